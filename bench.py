@@ -8,16 +8,20 @@ Default workload = BASELINE config 4, the one north_star quotes the target on: 1
 k=8, uniform fp32, seed 0xC4 (fits one MI355X: ~63 GB).  With --gpus N the same cloud is sharded by spatial
 slab over N ranks (strong scaling: total work fixed), one process per GPU, RCCL via torch.distributed.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full also measures what takes work of its own beyond the
+timed steps: the CPU baseline, the cold steps and the GPU's state sampled during the timed steps ("cpu_baseline", "cold", "box";
+null in a plain run).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 Started plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the process becomes a LAUNCHER: before torch is imported or
 any GPU call made it starts N fresh rank processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT),
 relays rank 0's JSON line, stops every rank as soon as one fails, and exits with the first failure's code.  Under
 torch.distributed.run the ranks are the launcher's and this file only reads the environment.
 
-Prints ONE JSON line on rank 0 (contract fields + "roofline" + "cpu_baseline" + per-phase detail).
+Prints ONE JSON line on rank 0 (contract fields + "roofline" + per-phase detail; with --full "cpu_baseline", "cold" and "box").
 """
 import argparse
 import json
@@ -138,6 +142,32 @@ def cpu_baseline(n_total, m_total, k, seed):
         "query_only_value": ms / (t2 - t1),
         "query_only_1thread_value": m1 / (t3 - t2),
     }
+
+
+DUMP_BYTES = 56 << 20          # --dump-outputs: bytes of .npy data in all, over every rank
+DUMP_SEED = 0xD0               # the row sample is drawn from this seed alone: the same rows for the same arguments
+
+
+def dump_outputs(out_dir, outputs, m, rank, world):
+    """--dump-outputs: the per-target arrays the timed path hands its caller, as left by the last timed step -- `idx` (int32 on the
+    device, written as float64: exact), `d2` (float64), `rgb` and `nrm` (float32), `pca_nrm` for C3 -- one row per resident target.
+    When all rows would not fit in DUMP_BYTES a fixed sample of them is written, sorted, and `rows` names the rows written (float64);
+    with more than one rank every file name carries `.rank<r>`."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    kinds = {name: (t, np.float32 if t.dtype == torch.float32 else np.float64) for name, t in outputs.items()}
+    row_bytes = 8 + sum(t.shape[1] * np.dtype(d).itemsize for t, d in kinds.values())
+    cap = DUMP_BYTES // world // row_bytes
+    if m <= cap:
+        rows = np.arange(m, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=cap, replace=False))
+    sel = torch.from_numpy(rows).to(next(iter(outputs.values())).device)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    np.save(os.path.join(out_dir, "rows%s.npy" % suffix), rows.astype(np.float64))
+    for name, (t, d) in kinds.items():
+        np.save(os.path.join(out_dir, "%s%s.npy" % (name, suffix)), t.index_select(0, sel).cpu().numpy().astype(d))
 
 
 class BoxSampler:
@@ -310,7 +340,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)      # (a C4 step is ~50 ms: five steps ended before the clocks had settled)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the cold steps (one GPU) and the GPU's state during the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (a fixed sample of rows beyond %d MiB)" % (DUMP_BYTES >> 20))
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal only: ranks may share one GPU, collectives staged through host memory")
     ap.add_argument("--exchange", default="native", choices=["native", "torch"],
@@ -330,6 +364,8 @@ def main():
                          "line says dry_run and carries no value")
     ap.add_argument("--fail-rank", type=int, default=-1, help="rehearsal of a failing rank: that rank exits with code 9 before the rendezvous")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if world == 0:
@@ -479,8 +515,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    box = BoxSampler(torch, local_rank)
-    # the first step after the first build: what a run that builds ONCE (reference src/pointsTransfer.cpp:259) pays for its search
+    box = BoxSampler(torch, local_rank) if args.full else None
+    # the first step after the first build: what a run that builds ONCE (reference src/pointsTransfer.cpp:259) pays for its search.  A plain
+    # run makes this query too, so that its warm-up and timed steps follow the same launches as ever; only --full reports it (`cold`)
     torch.cuda.synchronize(); tq = time.perf_counter()
     pt.query_blend_resident_dev(k, pkg.BLEND_MEAN, idx, d2, rgb, nrm)
     torch.cuda.synchronize(); first_query_wall = (time.perf_counter() - tq) * 1e3
@@ -491,24 +528,31 @@ def main():
     for _ in range(args.warmup):
         step(False)
     fence()
-    box.start()
+    if box is not None:
+        box.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step(True)
     fence()
     dt = time.perf_counter() - t0
-    box.stop()
+    if box is not None:
+        box.stop()
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = m_total * args.steps / dt
-    # COLD steps (one GPU): every build forgets what earlier builds of this resident cloud learnt ("forget": sampled bounding box, pooled
+    if args.dump_outputs:          # before the cold steps below overwrite the buffers
+        outputs = {"idx": idx, "d2": d2, "rgb": rgb, "nrm": nrm}
+        if with_pca:
+            outputs["pca_nrm"] = pnrm
+        dump_outputs(args.dump_outputs, outputs, m_loc, rank, world)
+    # COLD steps (one GPU, --full): every build forgets what earlier builds of this resident cloud learnt ("forget": sampled bounding box, pooled
     # passes, uniformity sample, cell size are decided afresh, as on a first build) -- buffers stay allocated, so this is the first build's
     # device work without hipMalloc.  `value` stays the warm figure (the contract's K timed steps); both are printed.
     cold = None
-    if world == 1:
+    if world == 1 and args.full:
         cs, cb = [], []
         for _ in range(3):
             torch.cuda.synchronize(); tc = time.perf_counter()
@@ -559,9 +603,9 @@ def main():
             "rank0": {"n_source": n_loc, "n_target": m_loc, "exchange": xstats},
             # the state of rank 0's GPU over the timed steps (sysfs, sampled by a host thread) and what the pass-1 scatter -- the kernel
             # whose time moves most from box to box -- reached on it: 12 B read + 16 B record + 2 B id written per source point
-            "box": dict(box.summary(), pass1_scatter_gbs=round(n_loc * 30 / (kavg[2] * 1e-3) / 1e9, 1) if kavg[2] > 0 else None),
+            "box": dict(box.summary(), pass1_scatter_gbs=round(n_loc * 30 / (kavg[2] * 1e-3) / 1e9, 1) if kavg[2] > 0 else None) if box is not None else None,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(n_total, m_total, k, seed)
         else:
             out["cpu_baseline"] = None

@@ -37,6 +37,21 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
+def ref_point_layout(oracle):
+    """Layout facts of the reference's own Point.h as the probe built from it prints them.  build() makes the probe only where the
+    reference tree is at hand (oracle/_ref/); its output is recorded in tests/golden/ref_point_layout.json, and a fresh probe run
+    must still equal that record."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "ref_point_layout.json")) as f:
+        recorded = json.load(f)
+    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "point_layout.json")):
+        live = oracle.ref_point_layout()
+        assert live == recorded, "the probe's output differs from tests/golden/ref_point_layout.json: %s" % live
+        return live
+    return recorded
+
+
+@pytest.fixture(scope="session")
 def pkg():
     import torch  # noqa: F401  -- before libpt_hip.so, so both share one HIP runtime
     import __graft_entry__ as g

@@ -33,8 +33,8 @@ def test_library_exports_every_declared_symbol(pkg):
         assert getattr(L, s) is not None
 
 
-def test_point_layout_matches_reference(pkg, oracle):
-    lay = oracle.ref_point_layout()                      # from the reference's own Point.h
+def test_point_layout_matches_reference(pkg, ref_point_layout):
+    lay = ref_point_layout                               # from the reference's own Point.h
     dt = pkg.POINT_DTYPE
     assert dt.itemsize == lay["sizeof"] == 80
     assert [dt.fields[n][1] for n in ("ver", "normal", "color", "U", "V")] == \

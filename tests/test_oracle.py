@@ -63,9 +63,9 @@ def test_metric_is_unfused(oracle):
         assert oracle.transformed_distance(a, b) == (dx * dx + dy * dy) + dz * dz
 
 
-def test_reference_point_layout(oracle):
-    # produced by oracle/_ref/point_layout, compiled from the reference's own src/Point.h
-    lay = oracle.ref_point_layout()
+def test_reference_point_layout(ref_point_layout):
+    # produced by oracle/_ref/point_layout, compiled from the reference's own src/Point.h (or its recorded output)
+    lay = ref_point_layout
     assert lay["sizeof"] == 80 and lay["alignof"] == 8
     assert (lay["off_ver"], lay["off_normal"], lay["off_color"], lay["off_U"], lay["off_V"]) == (0, 24, 48, 64, 72)
     assert lay["trivially_copyable"] == 1 and lay["standard_layout"] == 1

@@ -19,5 +19,5 @@ if [ -f tools/_ab/libpt_visits.so ]; then
   PT_HIP_LIB=tools/_ab/libpt_visits.so python3 tools/probe_wave_visits.py 1e9 5e7 32 8192 dup_runs=0 > $out/visits_no_dup_runs.log 2>&1
   echo visits done >> $out/progress.log
 fi
-python3 bench.py --workload C5 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --workload C5 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench.json 2> $out/bench.err
 find $out -name "*.csv" | head -20

@@ -15,5 +15,5 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS
 echo sq1 done >> $out/progress.log
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $out/sq2 -o sq2 -- python3 tools/run_step.py $wl 1 > $out/sq2.log 2>&1
 echo sq2 done >> $out/progress.log
-python3 bench.py --workload $wl > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --workload $wl > $out/bench.json 2> $out/bench.err
 find $out -name "*.csv" | head -40
