@@ -18,6 +18,7 @@
 #include <functional>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pt_api.h"
@@ -31,6 +32,64 @@ struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
 };
+
+// What the ids in the records and in finished lists mean, and so what the attribute table is indexed by
+enum class IdMode {
+  whole,          // the whole cloud: ids are indices into it
+  slab_global,    // a slab with its global indices (gidx): records carry them, the attribute table is the global one
+  slab_local,     // a slab with ascending gidx and "local_ids": records carry the point's POSITION in the slab's arrays (same order as the
+                  // global index), the attribute table is the slab's own n records, finished lists are translated through gidx
+};
+
+// What earlier builds of the resident cloud found out; a new cloud (or "forget") starts again from these defaults
+struct Learned {
+  bool bbox_guess_ok = true;   // big clouds: lay the grid out from a sampled bounding box (cleared when a guess failed)
+  bool pool_ok = true;         // big clouds, two-level sorts: pass 1 without its histogram pass (cleared when a bin outgrew its sampled region)
+  bool pool2_ok = true;        // pass 2 without its histogram: not failed yet on this cloud
+  bool uniform_seen = false;   // the last build of this cloud found it uniform
+  bool uniform_known = false;  // ... or a 1/64 sample taken before this cloud's first sort has answered the question (pt_grid.hip, uniform_probe_kernel)
+  // rebuilds start from the last build's cell size instead of searching again (a refined grid: one sort per step); finalize's occupancy checks it
+  double hint_h = 0.0, hint_rho_occ = 0.0;
+  int hint_refines = 0;
+};
+
+// Words of the pinned read-back buffers.  `counter` (device) and `h_counter` (host): 16 32-bit words, a count is read back into the host
+// word of the same number unless the entry says otherwise.  `h_bbox`: 10 64-bit words.
+enum Slot : int {
+  RB_SLAB_N = 0,       // 1 word: points a generated slab keeps (pt_build_synth, pt_targets_synth)
+  RB_ASCENDING = 1,    // 1 word: nonzero when a slab's gidx does not ascend (pt_build_soa_indexed)
+  RB_DEDUP = 2,        // 2 words: leaves, records (rebuild, dedup_leaves)
+  RB_TODO = 4,         // 1 word: targets the tile kernel left over (run_query)
+  RB_RETRY = 5,        // 1 word: blocks for the tile kernel's second chance (run_query)
+  RB_COUNT = 6,        // 1 word: packets of pt_pack_requests_dev / targets in reach of a chunk (pt_stream_query)
+  RB_TLIST = 7,        // 1 word: blocks that hold targets (run_query, sparse tile launch)
+  RB_OCC = 8,          // 2 words: sum, max (rebuild, occupied cells and the fullest one)
+  RB_NODES = 10,       // 1 word: nodes of the refinement so far (rebuild)
+  RB_PROBE = 11,       // 1 word, host only: the uniform probe's flag, read back from device word RB_PROBE_DEV (rebuild)
+  RB_WAVE = 12,        // 2 words: lengths of the plain and descending wave lists (run_query; copied back to the device for the kernels)
+  RB_WAVE_N = 14,      // 1 word, host only: length of the device-side list the wave kernel takes (run_query)
+  RB_POOL = 15,        // 1 word, host: the pooled passes' overflow flag, read back from SortTables::pool_flag (rebuild)
+  RB_PROBE_DEV = 15,   // 1 word, device: the uniform probe's flag (rebuild)
+  RB_WORDS = 16,
+  BB_BOX = 0,          // h_bbox, 6 words: the encoded bounding box {min xyz, max xyz} (source_bbox, rebuild's verified box)
+  BB_CHI2 = 6, BB_DOF = 7, BB_OCC = 8, BB_SAME = 9,     // h_bbox, 1 word each, from the uniform probe (rebuild): chi-square sum (x 1024), blocks it
+                                                        // is over, occupied cells (x 16), sample points in their wave's first block
+  BB_WORDS = 10,
+};
+
+// The branch on the coordinate type: f(x, Rec{}) with `xyz` typed as float (PT_F32) or double, const as given, Rec its record type.  by_coords
+// adds the fp16-resident source (__half, RecF): only the source's launchers exist for __half, everything else takes by_type
+template <class T, class V> using TypedPtr = std::conditional_t<std::is_const<V>::value, const T*, T*>;
+template <class V, class F>
+decltype(auto) by_type(int type, V* xyz, F&& f) {
+  if (type == PT_F32) return f((TypedPtr<float, V>)xyz, RecF{});
+  return f((TypedPtr<double, V>)xyz, RecD{});
+}
+template <class V, class F>
+decltype(auto) by_coords(int type, bool half, V* xyz, F&& f) {
+  if (half) return f((TypedPtr<__half, V>)xyz, RecF{});
+  return by_type(type, xyz, f);
+}
 
 }  // namespace
 
@@ -51,9 +110,12 @@ struct pt_ctx {
   int tile_contrast = 0;       // clouds with strong density contrast: 0 every target gets a wave (round 2), 1 the tile kernel first (k <= 24), what it cannot settle gets a wave
   size_t dev_bytes = 0;
 
-  // source cloud (slab-local when built from a slab)
+  // source cloud, slab-local when built from a slab (set by adopt_cloud, the one place a new cloud becomes resident)
   int src_type = -1;           // PT_F32 / PT_F64
   uint64_t n = 0, n_total = 0; // resident points; size of the attribute table
+  uint64_t synth_total = 0;    // a generated slab in local mode: the GENERATOR's point count (n_total is the slab's own then: its attribute table's length), which the clustered target generator needs
+  IdMode ids = IdMode::whole;
+  bool has_attr = false, built = false;
   DevBuf in_xyz, in_gidx, attr, rec, rec_tmp, cell_start;
   bool in_half = false;          // fp16 clouds: in_xyz holds the coordinates as fp16 (src_type says PT_F32: that is what they are sorted into)
   DevBuf xyz32;                  // ... and their fp32 image, made on demand for the few consumers of planar fp32 coordinates (PCA table, bake)
@@ -62,19 +124,16 @@ struct pt_ctx {
   bool rec32_valid = false;
   float e_src = 0.f;           // fp64 clouds: largest rounding error of a source coordinate stored as fp32
   DevBuf posattr;              // fp32 clouds: {position, attributes} by original index for the PCA pass, built on first use
-  bool has_gidx = false, has_attr = false, built = false, posattr_valid = false;
-  // slabs (round 4): "local_ids" asked for AND the slab's gidx strictly ascending -> the records carry the point's POSITION in the slab's arrays
-  // (same order as the global index), the attribute table may be the slab's own n records (attr_local), finished lists are translated through gidx
-  bool want_local_ids = false, local_mode = false, attr_local = false;
-  uint64_t synth_total = 0;    // a generated slab in local mode: the GENERATOR's point count (n_total is the slab's own then: its attribute table's length), which the clustered target generator needs
+  bool posattr_valid = false;
+  Learned learned;
+  bool slab() const { return ids != IdMode::whole; }
+  bool local_ids() const { return ids == IdMode::slab_local; }
+  bool attr_local() const { return ids == IdMode::slab_local && has_attr; }     // the table holds this slab's points by position
+  bool want_local_ids = false; // "local_ids": the next pt_build_soa_indexed / pt_build_synth of a slab builds it in local-id mode (ascending gidx)
   uint64_t guess_min_points = 8u << 20;   // clouds at least this large lay their grid out from a sampled bounding box
-  bool bbox_guess_ok = true;   // big clouds: lay the grid out from a sampled bounding box (cleared when a guess failed; reset by an upload)
   bool stream_bounds = true;   // pt_stream_query: later chunks are searched under the targets' current k-th distances and skipped when out of reach ("stream_bounds", a measurement switch)
   bool tile_bounds = false;    // run_query: bounds come with every target of the set (the tile kernel's bounded variant may take them)
-  bool uniform_known = false;  // ... or a 1/64 sample taken before this cloud's first sort has answered the question (pt_grid.hip, uniform_probe_kernel)
-  bool pool2_ok = true, pool2 = true, uniform_seen = false;   // pass 2 without its histogram: allowed ("pool2"), not failed yet on this cloud, and the last build of
-                               // this resident cloud found it uniform (reset by an upload together with pool_ok)
-  bool pool_ok = true;         // big clouds, two-level sorts: pass 1 without its histogram pass (cleared when a bin outgrew its sampled region; reset by an upload)
+  bool pool2 = true;           // pass 2 without its histogram on clouds found uniform: allowed ("pool2")
   int presort_refine = 1;                 // first builds of big non-uniform clouds refine the cell size from the sample, before the first sort ("presort_refine")
   uint64_t pool_min_points = 32u << 20;   // ... from this size up ("pool_min_points"; 0 switches the pooled pass 1 off)
   int n_cu = 256;              // compute units of the device: persistent workgroups of the pooled pass 1
@@ -92,10 +151,7 @@ struct pt_ctx {
   double refine_cpp = 2.0;              // ... and, in cells per point ("refine_cells_per_point")
   int refine_macros = PT_MAXBINS;       // finest grid the occupancy-driven refinement of h may ask for, in macro blocks (measured on the clustered
                                         // generator: beyond 1024 the extra sort pass costs more than the shorter scans save)
-  // rebuilds of the SAME resident cloud (pt_rebuild) start from the cell size the last build ended with instead of searching for it again
-  // (a refined grid costs one full sort per step of the search); the occupancy finalize reports checks the guess, a new cloud resets it
-  double hint_h = 0.0, hint_rho_occ = 0.0;
-  int hint_refines = 0, grid_hint = 1;
+  int grid_hint = 1;                    // rebuilds start from the cell size the last build ended with (Learned::hint_h)
   bool grid_capped = false;             // the last choose_grid ran into the macro-block limit: no finer grid exists
   int wave_force = 0;                   // 1: the heavy / light split also on clouds without density contrast (tests, tuning)
   uint32_t wave_min = 1;                // targets with at least this many points in their 27 nearest cells get a wave each (0: never; 1: all of
@@ -178,6 +234,20 @@ size_t recsize(int t) { return t == PT_F64 ? sizeof(RecD) : sizeof(RecF); }
 int finish(pt_ctx* c) {
   if (c->sync) HIPCHK(c, hipStreamSynchronize(c->stream));
   return PT_OK;
+}
+
+// A new source cloud is resident (its coordinates in in_xyz, its gidx in in_gidx; type -1: none is): the one transition every entry point
+// that replaces the source takes.  It sets identity and id mode, invalidates what was derived from the old cloud and forgets what earlier
+// builds learned.  The attribute table: `new_attr` -- the caller has just written one for this cloud.  Otherwise the resident table is KEPT
+// where the ids it is indexed by keep their meaning -- a global table under slabs built with their global indices (include/pt_api.h:
+// "attributes stay indexed by that global index") -- and DROPPED where they do not: a whole cloud, a local-id slab (entered or left),
+// the stream query's chunks.
+void adopt_cloud(pt_ctx* c, int type, uint64_t n, uint64_t n_total, IdMode ids, bool in_half, bool new_attr, uint64_t synth_total = 0) {
+  c->has_attr = new_attr || (c->has_attr && ids == IdMode::slab_global && c->ids != IdMode::slab_local);
+  c->src_type = type; c->n = n; c->n_total = n_total; c->synth_total = synth_total; c->ids = ids; c->in_half = in_half;
+  c->built = false;
+  c->posattr_valid = false; c->xyz32_valid = false;
+  c->learned = Learned{};
 }
 
 // carve the SortTables of one sort out of a single allocation
@@ -270,37 +340,29 @@ void choose_grid(pt_ctx* c, const double mn[3], const double mx[3], double force
   }
 }
 
-template <class T, class Rec>
 int run_source_sort(pt_ctx* c, uint64_t* bbox6_verify) {
-  const T* x = (const T*)c->in_xyz.p;
   hipError_t e = hipSuccess;
   c->stb.status = &e;
-  const Rec* r = pt_launch_grid_sort<T, Rec>(c->gp, x, x + c->n, x + 2 * c->n, (c->has_gidx && !c->local_mode) ? (const uint32_t*)c->in_gidx.p : nullptr, (uint32_t)c->n,
-                                             (Rec*)c->rec.p, (Rec*)c->rec_tmp.p, (uint32_t*)c->cell_start.p, c->stb, true, c->stream, bbox6_verify);
+  const bool ok = by_coords(c->src_type, c->in_half, (const void*)c->in_xyz.p, [&](auto x, auto rec) {
+    using Rec = decltype(rec);
+    return pt_launch_grid_sort(c->gp, x, x + c->n, x + 2 * c->n, c->ids == IdMode::slab_global ? (const uint32_t*)c->in_gidx.p : nullptr, (uint32_t)c->n,
+                               (Rec*)c->rec.p, (Rec*)c->rec_tmp.p, (uint32_t*)c->cell_start.p, c->stb, true, c->stream, bbox6_verify) != nullptr;
+  });
   c->stb.status = nullptr;
-  if (!r) return fail(c, PT_ERR_HIP, "grid build: a launch of the sort failed: %s", hipGetErrorString(e));
+  if (!ok) return fail(c, PT_ERR_HIP, "grid build: a launch of the sort failed: %s", hipGetErrorString(e));
   return PT_OK;
 }
 
 // bounding box of the resident cloud: every point (sample_stride = 1) or every sample_stride-th one
 int source_bbox(pt_ctx* c, uint32_t sample_stride, double (&mn)[3], double (&mx)[3]) {
   pt_launch_bbox_init((uint64_t*)c->bbox6.p, c->stream);
-  if (c->in_half) {
-    const __half* x = (const __half*)c->in_xyz.p;
-    if (sample_stride > 1) pt_launch_bbox_sample<__half>(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, sample_stride, (uint64_t*)c->bbox6.p, c->stream);
-    else pt_launch_bbox<__half>(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, (uint64_t*)c->bbox6.p, c->stream);
-  } else if (c->src_type == PT_F32) {
-    const float* x = (const float*)c->in_xyz.p;
-    if (sample_stride > 1) pt_launch_bbox_sample<float>(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, sample_stride, (uint64_t*)c->bbox6.p, c->stream);
-    else pt_launch_bbox<float>(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, (uint64_t*)c->bbox6.p, c->stream);
-  } else {
-    const double* x = (const double*)c->in_xyz.p;
-    if (sample_stride > 1) pt_launch_bbox_sample<double>(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, sample_stride, (uint64_t*)c->bbox6.p, c->stream);
-    else pt_launch_bbox<double>(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, (uint64_t*)c->bbox6.p, c->stream);
-  }
-  HIPCHK(c, hipMemcpyAsync(c->h_bbox, c->bbox6.p, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  by_coords(c->src_type, c->in_half, (const void*)c->in_xyz.p, [&](auto x, auto) {
+    if (sample_stride > 1) pt_launch_bbox_sample(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, sample_stride, (uint64_t*)c->bbox6.p, c->stream);
+    else pt_launch_bbox(x, x + c->n, x + 2 * c->n, (uint32_t)c->n, (uint64_t*)c->bbox6.p, c->stream);
+  });
+  HIPCHK(c, hipMemcpyAsync(c->h_bbox + BB_BOX, c->bbox6.p, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int a = 0; a < 3; ++a) { mn[a] = pt_bbox_decode(c->h_bbox[a]); mx[a] = pt_bbox_decode(c->h_bbox[3 + a]); }
+  for (int a = 0; a < 3; ++a) { mn[a] = pt_bbox_decode(c->h_bbox[BB_BOX + a]); mx[a] = pt_bbox_decode(c->h_bbox[BB_BOX + 3 + a]); }
   for (int a = 0; a < 3; ++a)
     if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) return fail(c, PT_ERR_ARG, "source coordinates are not finite");
   return PT_OK;
@@ -332,7 +394,7 @@ int rebuild(pt_ctx* c) {
   c->st.bbox_guess = 0;
   c->st.uniform_probe = 0;
   if (c->n) {
-    guessed = c->bbox_guess_ok && c->n >= c->guess_min_points;
+    guessed = c->learned.bbox_guess_ok && c->n >= c->guess_min_points;
     { int r = source_bbox(c, guessed ? 1024u : 1u, mn, mx); if (r != PT_OK) return r; }
   }
   // Grid choice.  The first guess assumes the cloud fills its bounding box; finalize counts the non-empty cells, and when
@@ -340,7 +402,7 @@ int rebuild(pt_ctx* c) {
   // beyond what the dense cell table allows (choose_grid coarsens again if the macro-block limit is hit).
   double force_h = 0.0;
   bool hinted = false;
-  if (c->grid_hint && c->adaptive && c->hint_h > 0.0) { force_h = c->hint_h; hinted = true; }
+  if (c->grid_hint && c->adaptive && c->learned.hint_h > 0.0) { force_h = c->learned.hint_h; hinted = true; }
   uint32_t nblocks = 0;
   size_t ncells = 0;
   c->st.n_refine = 0;
@@ -374,7 +436,7 @@ int rebuild(pt_ctx* c) {
     // big clouds on the two-level sort: pass 1 takes its bin regions from a sample instead of a histogram pass of its own (pt_grid.hip,
     // scatter_pool_kernel); its output -- the records array -- then carries slack between the bins and a scratch area
     uint64_t pool_records = 0;
-    if (c->pool_ok && c->pool_min_points && c->n >= c->pool_min_points && nblocks > PT_MAXBINS && !pt_sort_group_shift(nblocks))
+    if (c->learned.pool_ok && c->pool_min_points && c->n >= c->pool_min_points && nblocks > PT_MAXBINS && !pt_sort_group_shift(nblocks))
       pool_records = pt_sort_pool_records((uint32_t)c->n, nblocks / PT_MACRO_BLOCKS, (uint32_t)c->n_cu, recsize(c->src_type));
     // a resident cloud whose last build found it uniform (no refinement of the cell size, occupied cells at rho) takes pass 2 without its
     // histogram too: block regions from the macro counts (pt_grid.hip, pool2_sizes_kernel); the pass-2 output then carries slack.
@@ -385,23 +447,23 @@ int rebuild(pt_ctx* c) {
     // is refined BEFORE the first sort, by the rule the occupancy count is held to below, and the sample is asked again on the finer grid
     // (at most three times: a fraction of a millisecond each instead of a sort each; "presort_refine").  The sort's own count still decides.
     const bool presort_again = presort_iters > 0 && presort_iters < 3 && iter == 0 && nsorts == 0;
-    if (((!c->uniform_known && force_h == 0.0) || presort_again) && iter == 0 && c->pool2_ok && c->pool2 && c->adaptive && c->pool_min_points && c->n >= c->pool_min_points &&
+    if (((!c->learned.uniform_known && force_h == 0.0) || presort_again) && iter == 0 && c->learned.pool2_ok && c->pool2 && c->adaptive && c->pool_min_points && c->n >= c->pool_min_points &&
         nblocks > PT_MAXBINS && !pt_sort_group_shift(nblocks)) {
       int olo[3], ohi[3];
       for (int a = 0; a < 3; ++a) { olo[a] = pad_cells[a]; ohi[a] = c->gp.dim[a] - pad_cells[a]; }
-      uint32_t* pflag = (uint32_t*)c->counter.p + 15;
+      uint32_t* pflag = (uint32_t*)c->counter.p + RB_PROBE_DEV;
       uint32_t* scratch = (uint32_t*)c->cell_start.p;                  // (written by finalize later; nblocks + nblocks / 512 words are a fraction of it)
-      if (c->in_half) { const __half* x = (const __half*)c->in_xyz.p; pt_launch_uniform_probe<__half>(c->gp, x, x + c->n, x + 2 * c->n, (uint32_t)c->n, olo, ohi, scratch, pflag, c->stream); }
-      else if (c->src_type == PT_F32) { const float* x = (const float*)c->in_xyz.p; pt_launch_uniform_probe<float>(c->gp, x, x + c->n, x + 2 * c->n, (uint32_t)c->n, olo, ohi, scratch, pflag, c->stream); }
-      else { const double* x = (const double*)c->in_xyz.p; pt_launch_uniform_probe<double>(c->gp, x, x + c->n, x + 2 * c->n, (uint32_t)c->n, olo, ohi, scratch, pflag, c->stream); }
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 11, pflag, 4, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->h_bbox + 6, scratch + pt_uniform_probe_acc_offset(nblocks), 32, hipMemcpyDeviceToHost, c->stream));     // (h_bbox: 10 pinned 64-bit words, 6 of them the box)
+      by_coords(c->src_type, c->in_half, (const void*)c->in_xyz.p, [&](auto x, auto) {
+        pt_launch_uniform_probe(c->gp, x, x + c->n, x + 2 * c->n, (uint32_t)c->n, olo, ohi, scratch, pflag, c->stream);
+      });
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_PROBE, pflag, 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h_bbox + BB_CHI2, scratch + pt_uniform_probe_acc_offset(nblocks), 32, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
       if (!presort_again) {
-        const double chi2 = (double)c->h_bbox[6] / 1024.0, dof = (double)c->h_bbox[7];
-        c->uniform_seen = c->h_counter[11] == 0 && dof > 0.0 && chi2 <= dof + 6.0 * std::sqrt(2.0 * dof) + 16.0;
-        c->uniform_known = true;
-        c->st.uniform_probe = c->uniform_seen ? 1 : -1;
+        const double chi2 = (double)c->h_bbox[BB_CHI2] / 1024.0, dof = (double)c->h_bbox[BB_DOF];
+        c->learned.uniform_seen = c->h_counter[RB_PROBE] == 0 && dof > 0.0 && chi2 <= dof + 6.0 * std::sqrt(2.0 * dof) + 16.0;
+        c->learned.uniform_known = true;
+        c->st.uniform_probe = c->learned.uniform_seen ? 1 : -1;
       }
       // A cloud stored in SPATIAL order (scan lines, tiles, a previous sort) shows a sample of consecutive points a few crowded blocks and nothing
       // in between: neither the regions of the pooled passes nor the occupancy estimate below can be taken from it.  It gives itself away -- of 64
@@ -410,14 +472,14 @@ int rebuild(pt_ctx* c) {
       if (!presort_again) {
         const uint32_t stride = std::max<uint32_t>(16u, std::min<uint32_t>(256u, (uint32_t)c->n >> 22));
         const double sampled = (double)c->n / stride;
-        c->st.ordered_input = (double)c->h_bbox[9] > 0.25 * sampled ? 1 : 0;
-        if (c->st.ordered_input) { c->pool_ok = false; c->pool2_ok = false; c->uniform_seen = false; c->st.uniform_probe = -1; pool_records = 0; }
+        c->st.ordered_input = (double)c->h_bbox[BB_SAME] > 0.25 * sampled ? 1 : 0;
+        if (c->st.ordered_input) { c->learned.pool_ok = false; c->learned.pool2_ok = false; c->learned.uniform_seen = false; c->st.uniform_probe = -1; pool_records = 0; }
       }
-      const double occ_ub = (double)c->h_bbox[8] / 16.0;
+      const double occ_ub = (double)c->h_bbox[BB_OCC] / 16.0;
       const double rho_lb = occ_ub > 0.0 ? (double)c->n / occ_ub : 0.0;
-      if (getenv("PT_DEBUG_PRESORT")) fprintf(stderr, "uniform probe: flag %u chi2 %.1f dof %.0f same-block %llu\n", c->h_counter[11], (double)c->h_bbox[6] / 1024.0, (double)c->h_bbox[7], (unsigned long long)c->h_bbox[9]);
-      if (getenv("PT_DEBUG_PRESORT")) fprintf(stderr, "presort probe: grid %d %d %d h %.6g occ_ub %.0f rho_lb %.2f iters %d uniform %d\n", c->gp.dim[0], c->gp.dim[1], c->gp.dim[2], c->gp.h, occ_ub, rho_lb, presort_iters, (int)c->uniform_seen);
-      if (c->presort_refine && !c->uniform_seen && !c->st.ordered_input && presort_iters < 3 && rho_lb > 1.5 * c->rho) {
+      if (getenv("PT_DEBUG_PRESORT")) fprintf(stderr, "uniform probe: flag %u chi2 %.1f dof %.0f same-block %llu\n", c->h_counter[RB_PROBE], (double)c->h_bbox[BB_CHI2] / 1024.0, (double)c->h_bbox[BB_DOF], (unsigned long long)c->h_bbox[BB_SAME]);
+      if (getenv("PT_DEBUG_PRESORT")) fprintf(stderr, "presort probe: grid %d %d %d h %.6g occ_ub %.0f rho_lb %.2f iters %d uniform %d\n", c->gp.dim[0], c->gp.dim[1], c->gp.dim[2], c->gp.h, occ_ub, rho_lb, presort_iters, (int)c->learned.uniform_seen);
+      if (c->presort_refine && !c->learned.uniform_seen && !c->st.ordered_input && presort_iters < 3 && rho_lb > 1.5 * c->rho) {
         const double h_old = c->gp.h;
         const int d0 = c->gp.dim[0], d1 = c->gp.dim[1], d2 = c->gp.dim[2];
         const double h_new = h_old * std::pow(c->rho * 1.25 / rho_lb, 1.0 / 2.2);
@@ -438,7 +500,7 @@ int rebuild(pt_ctx* c) {
       presort_iters = presort_iters ? 3 : 0;       // (asked for the last time)
     }
     uint64_t pool2_records = 0;
-    if (c->pool2_ok && c->pool2 && c->uniform_seen && nblocks > PT_MAXBINS && !pt_sort_group_shift(nblocks) && c->n)
+    if (c->learned.pool2_ok && c->pool2 && c->learned.uniform_seen && nblocks > PT_MAXBINS && !pt_sort_group_shift(nblocks) && c->n)
       pool2_records = pt_sort_pool2_records(pool_records ? c->n + (uint64_t)(nblocks / PT_MACRO_BLOCKS) * c->n_cu * 128u : c->n, nblocks, recsize(c->src_type));
     RES(c, c->rec, std::max<size_t>(std::max<uint64_t>(c->n, pool_records), 1) * recsize(c->src_type));
     RES(c, c->rec_tmp, std::max<size_t>(std::max<uint64_t>(c->n, pool2_records), 1) * recsize(c->src_type));
@@ -452,14 +514,14 @@ int rebuild(pt_ctx* c) {
       RES(c, c->rec32, c->n * sizeof(RecF));
       c->stb.shadow32 = (RecF*)c->rec32.p;
     }
-    uint32_t* occ = (uint32_t*)c->counter.p + 8;
+    uint32_t* occ = (uint32_t*)c->counter.p + RB_OCC;
     c->stb.occupied = c->adaptive ? c->stb.block_count : nullptr;     // block_count is dead once block_start exists
     const bool verify = guessed && iter == 0;
     if (verify) pt_launch_bbox_init((uint64_t*)c->bbox6.p, c->stream);
     uint64_t* bv = verify ? (uint64_t*)c->bbox6.p : nullptr;
     ++nsorts; c->st.n_sorts = nsorts;
-    { const int r = c->in_half ? run_source_sort<__half, RecF>(c, bv) : (c->src_type == PT_F32 ? run_source_sort<float, RecF>(c, bv) : run_source_sort<double, RecD>(c, bv)); if (r != PT_OK) return r; }
-    c->h_counter[15] = 0;
+    { const int r = run_source_sort(c, bv); if (r != PT_OK) return r; }
+    c->h_counter[RB_POOL] = 0;
     // ONE read-back per sort (round 4; there were up to three, each a drained pipeline -- a third of a 10 M-point rebuild): the pooled
     // passes' overflow flag, the verified bounding box and finalize's occupancy travel together; the occupancy sum is queued before it is
     // known whether a guess failed (then it sums whatever an aborted finalize left and is not looked at)
@@ -467,44 +529,44 @@ int rebuild(pt_ctx* c) {
     if (want_occ) {
       HIPCHK(c, hipMemsetAsync(occ, 0, 8, c->stream));
       pt_launch_sum_u32(c->stb.block_count, nblocks, occ, c->stream);
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 8, occ, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_OCC, occ, 8, hipMemcpyDeviceToHost, c->stream));
     }
     if (pool_records || pool2_records)     // did every bin stay inside the region its estimate gave it?
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 15, c->stb.pool_flag, 4, hipMemcpyDeviceToHost, c->stream));
-    if (verify) HIPCHK(c, hipMemcpyAsync(c->h_bbox, c->bbox6.p, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_POOL, c->stb.pool_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    if (verify) HIPCHK(c, hipMemcpyAsync(c->h_bbox + BB_BOX, c->bbox6.p, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (want_occ || pool_records || pool2_records || verify) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (verify) {
       bool inside = true, finite = true;
       for (int a = 0; a < 3; ++a) {
-        mn[a] = pt_bbox_decode(c->h_bbox[a]); mx[a] = pt_bbox_decode(c->h_bbox[3 + a]);      // exact from here on
+        mn[a] = pt_bbox_decode(c->h_bbox[BB_BOX + a]); mx[a] = pt_bbox_decode(c->h_bbox[BB_BOX + 3 + a]);      // exact from here on
         finite = finite && std::isfinite(mn[a]) && std::isfinite(mx[a]);
         inside = inside && mn[a] >= c->gp.bbmin[a] && mx[a] <= c->gp.bbmin[a] + c->gp.dim[a] * c->gp.h;
       }
       if (!finite) return fail(c, PT_ERR_ARG, "source coordinates are not finite");
       c->st.bbox_guess = inside ? 1 : -1;
       if (!inside) {          // the sample missed part of the cloud: start over from the exact box, no more guessing for this cloud
-        c->bbox_guess_ok = false;
+        c->learned.bbox_guess_ok = false;
         guessed = false;
         force_h = 0.0;
-        if (c->st.uniform_probe) { c->uniform_known = false; c->uniform_seen = false; }      // (the sample was binned on the wrong grid: asked again on the exact one)
+        if (c->st.uniform_probe) { c->learned.uniform_known = false; c->learned.uniform_seen = false; }      // (the sample was binned on the wrong grid: asked again on the exact one)
         presort_iters = 0; presort_unverified = false; c->st.n_refine = 0; c->st.presort_refine = 0;
-        if (c->h_counter[15] & 1u) c->pool_ok = false;
-        if (c->h_counter[15] & 2u) c->pool2_ok = false;
+        if (c->h_counter[RB_POOL] & 1u) c->learned.pool_ok = false;
+        if (c->h_counter[RB_POOL] & 2u) c->learned.pool2_ok = false;
         --iter;
         continue;
       }
     }
-    if (c->h_counter[15]) {                       // a bin outgrew its region (the sample missed a cluster; a macro block is not uniform inside):
-      if (c->h_counter[15] & 1u) { c->pool_ok = false; pool_failed = true; }       // the same grid again with exact bins, and no more pooling of
-      if (c->h_counter[15] & 2u) { c->pool2_ok = false; pool2_failed = true; }     // that pass for this cloud
+    if (c->h_counter[RB_POOL]) {                  // a bin outgrew its region (the sample missed a cluster; a macro block is not uniform inside):
+      if (c->h_counter[RB_POOL] & 1u) { c->learned.pool_ok = false; pool_failed = true; }       // the same grid again with exact bins, and no more pooling of
+      if (c->h_counter[RB_POOL] & 2u) { c->learned.pool2_ok = false; pool2_failed = true; }     // that pass for this cloud
       guessed = false;                            // (the box is exact by now, or was never guessed)
       --iter;
       continue;
     }
     c->st.rho_occupied = 0.0;
     if (!want_occ) break;
-    const double occupied = std::max<double>(1.0, c->h_counter[8]);
-    max_cell = c->h_counter[9];
+    const double occupied = std::max<double>(1.0, c->h_counter[RB_OCC]);
+    max_cell = c->h_counter[RB_OCC + 1];
     c->st.rho_occupied = (double)c->n / occupied;
     if (presort_unverified) {
       // The sample's bound holds for points in random order.  A cloud stored in SPATIAL order shows the sample (runs of consecutive points) a few
@@ -514,13 +576,13 @@ int rebuild(pt_ctx* c) {
       if (c->st.rho_occupied < 0.4 * c->rho) {
         c->st.presort_refine = -presort_iters;
         presort_iters = 3; force_h = 0.0; c->st.n_refine = 0; iter = -1;
-        c->pool_ok = false; c->pool2_ok = false;          // (a sample that misjudged the occupancy misjudges the regions too)
+        c->learned.pool_ok = false; c->learned.pool2_ok = false;          // (a sample that misjudged the occupancy misjudges the regions too)
         continue;
       }
     }
     if (hinted) {
-      if (c->st.rho_occupied <= 1.25 * c->hint_rho_occ) { c->st.n_refine = c->hint_refines; break; }     // the grid the last build settled on still fits
-      hinted = false; c->hint_h = 0.0; force_h = 0.0; c->st.n_refine = 0; iter = -1;                      // it does not (the resident cloud was changed under us): search again
+      if (c->st.rho_occupied <= 1.25 * c->learned.hint_rho_occ) { c->st.n_refine = c->learned.hint_refines; break; }     // the grid the last build settled on still fits
+      hinted = false; c->learned.hint_h = 0.0; force_h = 0.0; c->st.n_refine = 0; iter = -1;                      // it does not (the resident cloud was changed under us): search again
       continue;
     }
     if (iter >= 3 || c->st.rho_occupied <= 1.5 * c->rho) break;
@@ -535,7 +597,7 @@ int rebuild(pt_ctx* c) {
     if (!changed || !finer) break;                 // already at the resolution limit (or nothing left to split)
     ++c->st.n_refine;
   }
-  if (c->st.n_refine > 0 && !hinted) { c->hint_h = c->gp.h; c->hint_rho_occ = c->st.rho_occupied; c->hint_refines = c->st.n_refine; }
+  if (c->st.n_refine > 0 && !hinted) { c->learned.hint_h = c->gp.h; c->learned.hint_rho_occ = c->st.rho_occupied; c->learned.hint_refines = c->st.n_refine; }
   // ---- heavy cells get sub-grids (pt_refine.hip): only clouds whose fullest cell is over the threshold pay anything here ----
   c->n_nodes = 0; c->refine_levels = 0;
   if (c->refine_threshold >= 1.0 && c->adaptive && c->n && (double)max_cell > c->refine_threshold) {
@@ -547,18 +609,20 @@ int rebuild(pt_ctx* c) {
     RES(c, c->near_node, ncells + 16);
     HIPCHK(c, hipMemsetAsync(c->near_node.p, 0, ncells, c->stream));
     RES(c, c->nodes, (size_t)cap * PT_NODE_WORDS * sizeof(uint32_t));
-    uint32_t* cnt = (uint32_t*)c->counter.p + 10;
+    uint32_t* cnt = (uint32_t*)c->counter.p + RB_NODES;
     HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
     pt_launch_heavy_cells(c->gp, (const uint32_t*)c->cell_start.p, (uint32_t)ncells, thr, (uint32_t*)c->cell_node.p, cnt, cap, (uint32_t*)c->nodes.p, (uint8_t*)c->near_node.p, c->stream);
     uint32_t n0 = 0, n1 = 0;
     for (int level = 0; level < PT_REFINE_DEPTH; ++level) {
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 10, cnt, 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_NODES, cnt, 4, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));                       // one read-back per level: how many nodes the level has
-      n1 = std::min(c->h_counter[10], cap);
+      n1 = std::min(c->h_counter[RB_NODES], cap);
       HIPCHK(c, hipMemcpyAsync(cnt, &n1, 4, hipMemcpyHostToDevice, c->stream));      // (a counter that ran past the capacity is put back)
       if (n1 == n0) break;
-      if (c->src_type == PT_F32) pt_launch_refine_nodes<RecF>(c->gp, (RecF*)c->rec.p, (RecF*)c->rec_tmp.p, n0, n1, (uint32_t*)c->nodes.p, c->stream);
-      else pt_launch_refine_nodes<RecD>(c->gp, (RecD*)c->rec.p, (RecD*)c->rec_tmp.p, n0, n1, (uint32_t*)c->nodes.p, c->stream);
+      by_type(c->src_type, c->in_xyz.p, [&](auto, auto rec) {     // (fp16-resident clouds are PT_F32: RecF)
+        using Rec = decltype(rec);
+        pt_launch_refine_nodes(c->gp, (Rec*)c->rec.p, (Rec*)c->rec_tmp.p, n0, n1, (uint32_t*)c->nodes.p, c->stream);
+      });
       const bool last = level + 1 == PT_REFINE_DEPTH;
       pt_launch_heavy_subcells(n0, n1, last ? 0xFFFFFFFFu : thr, cnt, cap, (uint32_t*)c->nodes.p, c->stream);
       c->refine_levels = (uint32_t)level + 1;
@@ -570,13 +634,15 @@ int rebuild(pt_ctx* c) {
     c->st.dup_leaves = 0;
     if (n1 && c->dup_runs) {
       static_assert(PT_MAX_K <= PT_DUP_KEEP, "a leaf's front must hold every point a query may return from it");
-      uint32_t* dst = (uint32_t*)c->counter.p + 2;
+      uint32_t* dst = (uint32_t*)c->counter.p + RB_DEDUP;
       HIPCHK(c, hipMemsetAsync(dst, 0, 8, c->stream));
-      if (c->src_type == PT_F32) pt_launch_dedup_leaves<RecF>((RecF*)c->rec.p, (RecF*)c->rec_tmp.p, 0, n1, (uint32_t*)c->nodes.p, dst, c->stream);
-      else pt_launch_dedup_leaves<RecD>((RecD*)c->rec.p, (RecD*)c->rec_tmp.p, 0, n1, (uint32_t*)c->nodes.p, dst, c->stream);
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 2, dst, 8, hipMemcpyDeviceToHost, c->stream));
+      by_type(c->src_type, c->in_xyz.p, [&](auto, auto rec) {     // (fp16-resident clouds are PT_F32: RecF)
+        using Rec = decltype(rec);
+        pt_launch_dedup_leaves((Rec*)c->rec.p, (Rec*)c->rec_tmp.p, 0, n1, (uint32_t*)c->nodes.p, dst, c->stream);
+      });
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_DEDUP, dst, 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      c->st.dup_leaves = (int32_t)std::min<uint32_t>(c->h_counter[2], 0x7FFFFFFFu);
+      c->st.dup_leaves = (int32_t)std::min<uint32_t>(c->h_counter[RB_DEDUP], 0x7FFFFFFFu);
     }
     if (c->src_type == PT_F64 && c->stb.shadow32 && n1) pt_launch_reshadow((const RecD*)c->rec.p, (uint32_t)c->n, c->stb.shadow32, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -592,9 +658,9 @@ int rebuild(pt_ctx* c) {
   }
   // what the next build of this resident cloud may assume: a cloud whose occupied cells hold about rho points without any refinement of
   // the cell size is uniform enough for block regions sized from the macro counts (verified again by that build's overflow flag)
-  c->uniform_seen = c->adaptive && c->n && c->st.n_refine == 0 && !c->grid_capped && c->st.rho_occupied > 0.0 &&
+  c->learned.uniform_seen = c->adaptive && c->n && c->st.n_refine == 0 && !c->grid_capped && c->st.rho_occupied > 0.0 &&
                     c->st.rho_occupied <= 1.25 * c->rho / (1.0 - std::exp(-c->rho));       // (a uniform cloud's occupied cells hold rho / (1 - e^-rho))
-  c->uniform_known = true;                                      // (what a finished build found outranks the sample)
+  c->learned.uniform_known = true;                                      // (what a finished build found outranks the sample)
   c->built = true;
   c->st.n_source = c->n;
   c->st.grid_dim[0] = c->gp.dim[0]; c->st.grid_dim[1] = c->gp.dim[1]; c->st.grid_dim[2] = c->gp.dim[2];
@@ -675,7 +741,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
   // settle is on the todo list afterwards.  fp64 clouds: the LDS image is the fp32 shadow of the sorted records, the exact
   // 32-byte records are fetched for the few candidates that reach the ranking pass.
   std::function<void()> retry_launch;                   // the large-geometry launch over the blocks the small one passed on
-  bool retry_pending = false;                           // ... its block count is still on its way to the host (see group_f32 / group_f64)
+  bool retry_pending = false;                           // ... its block count is still on its way to the host (see group)
   const bool defer_retry = c->wave_min > 0 && c->wave_min <= 1 && c->n_nodes == 0 && (k > 16 || c->sync) && k <= 64;      // the leftovers get a wave each, sized by a read-back
   auto tile_launches = [&](const RecF* src32, const RecF* tgt32, const RecD* src64, const RecD* tgt64, uint32_t* todo_n) -> int {
     const double cells = (double)c->gp.dim[0] * c->gp.dim[1] * c->gp.dim[2];
@@ -695,14 +761,14 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
     uint32_t nlist = 0;
     if (c->tile_sparse == 1 || (c->tile_sparse == 2 && empty_grid)) {
       RES(c, c->tlist, (size_t)c->gp.nblocks * sizeof(uint32_t));
-      uint32_t* lcnt = (uint32_t*)c->counter.p + 7;
+      uint32_t* lcnt = (uint32_t*)c->counter.p + RB_TLIST;
       pt_launch_tblock_list(c->ttb.block_start, (uint32_t)c->gp.nblocks, (uint32_t*)c->tlist.p, lcnt, c->stream);
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 7, lcnt, 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_TLIST, lcnt, 4, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      blist = (const uint32_t*)c->tlist.p; nlist = c->h_counter[7];
+      blist = (const uint32_t*)c->tlist.p; nlist = c->h_counter[RB_TLIST];
       if (!nlist) return PT_OK;
     }
-    uint32_t* retry_n = (uint32_t*)c->counter.p + 5;
+    uint32_t* retry_n = (uint32_t*)c->counter.p + RB_RETRY;
     if (second_chance) {
       HIPCHK(c, hipMemsetAsync(retry_n, 0, 4, c->stream));
       RES(c, c->retry, (size_t)c->gp.nblocks * sizeof(uint32_t));
@@ -714,19 +780,19 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       retry_launch = [=]() {
         pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
                            0, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr,
-                           (const uint32_t*)c->retry.p, c->h_counter[5], nullptr, nullptr, src64, tgt64, c->e_src, c->stream, bound2_dev);
+                           (const uint32_t*)c->retry.p, c->h_counter[RB_RETRY], nullptr, nullptr, src64, tgt64, c->e_src, c->stream, bound2_dev);
       };
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 5, retry_n, 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_RETRY, retry_n, 4, hipMemcpyDeviceToHost, c->stream));
       // (round 4) when the leftover pass reads the todo list's length anyway -- one wave per leftover target -- the two counts share that
       // read-back: a 1 M-target query spent a third of its time in two drained pipelines.  Otherwise: one short read-back here; usually
       // 0 blocks and no launch
       if (defer_retry) { retry_pending = true; return PT_OK; }
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (c->h_counter[5]) retry_launch();
+      if (c->h_counter[RB_RETRY]) retry_launch();
     }
     return PT_OK;
   };
-  uint32_t* todo_n = (uint32_t*)c->counter.p + 4;
+  uint32_t* todo_n = (uint32_t*)c->counter.p + RB_TODO;
   // what the tile kernel does not take (or leaves over) goes to the 8-lanes-per-target kernel: the plain one, or -- when the build
   // refined heavy cells -- the one that descends into their sub-grids instead of scanning them end to end
   const bool hier = c->n_nodes > 0;
@@ -739,7 +805,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
   // buffers of the split: marks (one byte per target), the two ordered lists (m words together), per-tile offsets and scan scratch
   const uint32_t mtiles = pt_mark_tiles(m);
   uint8_t* heavy = nullptr;
-  uint32_t *hlist = nullptr, *hoff1 = nullptr, *hoff2 = nullptr, *hscan = nullptr, *hcnt = (uint32_t*)c->counter.p + 12;
+  uint32_t *hlist = nullptr, *hoff1 = nullptr, *hoff2 = nullptr, *hscan = nullptr, *hcnt = (uint32_t*)c->counter.p + RB_WAVE;
   if (wave) {
     RES(c, c->heavy, (size_t)m * sizeof(uint32_t) + (((size_t)m + 15) & ~(size_t)15) + ((size_t)mtiles + 4) * 3 * sizeof(uint32_t) + 64);
     hlist = (uint32_t*)c->heavy.p;
@@ -756,138 +822,86 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
   // marks -> ordered lists; one read-back of the two lengths.  false: a HIP call failed (the caller's hipGetLastError reports it)
   auto wave_lists = [&]() -> bool {
     pt_launch_mark_count(heavy, m, hoff1, hoff2, hscan, c->stream);
-    if (hipMemcpyAsync(c->h_counter + 12, hoff1 + mtiles, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->h_counter + 13, hoff2 + mtiles, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return false;
-    c->st.n_wave = c->h_counter[12] + c->h_counter[13];
+    if (hipMemcpyAsync(c->h_counter + RB_WAVE, hoff1 + mtiles, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->h_counter + RB_WAVE + 1, hoff2 + mtiles, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return false;
+    c->st.n_wave = c->h_counter[RB_WAVE] + c->h_counter[RB_WAVE + 1];
     if (!c->st.n_wave) return false;
-    pt_launch_mark_write(heavy, m, hoff1, hoff2, hlist, hlist + c->h_counter[12], c->stream);
-    return hipMemcpyAsync(hcnt, c->h_counter + 12, 8, hipMemcpyHostToDevice, c->stream) == hipSuccess;      // the kernels read their list length from the device
+    pt_launch_mark_write(heavy, m, hoff1, hoff2, hlist, hlist + c->h_counter[RB_WAVE], c->stream);
+    return hipMemcpyAsync(hcnt, c->h_counter + RB_WAVE, 8, hipMemcpyHostToDevice, c->stream) == hipSuccess;      // the kernels read their list length from the device
   };
-  auto group_f32 = [&](const RecF* tg, const double* bnd, const uint32_t* list, const uint32_t* list_n) {
-    if (wave && c->wave_min <= 1) {
-      // every target gets a wave (measured on the clustered generator: the group kernel loses to it even on the sparse targets there,
-      // and marking 50 M targets costs it 70 ms): no group kernel at all.  Without refined cells the list is the input list;
-      // with them, a one-load-per-target pass marks who needs the descending variant.
-      if (!hier) {
-        uint32_t cnt = m;
-        if (list) {                                           // a device-side list (what the tile kernel left over): its length sizes the launch
-          if (hipMemcpyAsync(c->h_counter + 14, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
-          if (retry_pending) {                                // the second-chance blocks' count came with it: their launch may add to the list
-            retry_pending = false;
-            if (c->h_counter[5]) {
-              retry_launch();
-              if (hipMemcpyAsync(c->h_counter + 14, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
+  // the typed half: target sort, tile launches, group / wave kernels, the blend of what the tile kernel handed over
+  const int typed = by_type(ttype, txyz, [&](auto x, auto rec) -> int {
+    using Rec = decltype(rec);
+    const Rec* src = (const Rec*)c->rec.p;
+    const uint32_t* cell_start = (const uint32_t*)c->cell_start.p;
+    // the two wave lists: plain variant for the first, descending variant for the second (every marked target is on one of them);
+    // blend: the attributes are blended in the same launches
+    auto wave_pair = [&](const Rec* tg, const double* bnd, bool blend) {
+      const uint32_t n1 = c->h_counter[RB_WAVE], n2 = c->h_counter[RB_WAVE + 1];
+      const Attr* at = blend ? wattr : nullptr;
+      const uint32_t nat = blend ? wnattr : 0;
+      const int mode = blend ? wmode : 0;
+      float *rgb = blend ? wrgb : nullptr, *nrm = blend ? wnrm : nullptr;
+      pt_launch_knn_wave<Rec>(c->gp, src, cell_start, nullptr, nullptr, 0xFFFFFFFFu, tg, n1, k, bnd, idx_dev, d2_dev, hlist, hcnt, c->stream, at, nat, mode, rgb, nrm);
+      pt_launch_knn_wave<Rec>(c->gp, src, cell_start, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold, tg, n2, k, bnd,
+                              idx_dev, d2_dev, hlist + n1, hcnt + 1, c->stream, at, nat, mode, rgb, nrm);
+    };
+    auto group = [&](const Rec* tg, const double* bnd, const uint32_t* list, const uint32_t* list_n) {
+      if (wave && c->wave_min <= 1) {
+        // every target gets a wave (measured on the clustered generator: the group kernel loses to it even on the sparse targets there,
+        // and marking 50 M targets costs it 70 ms): no group kernel at all.  Without refined cells the list is the input list;
+        // with them, a one-load-per-target pass marks who needs the descending variant.
+        if (!hier) {
+          uint32_t cnt = m;
+          if (list) {                                         // a device-side list (what the tile kernel left over): its length sizes the launch
+            if (hipMemcpyAsync(c->h_counter + RB_WAVE_N, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
+            if (retry_pending) {                              // the second-chance blocks' count came with it: their launch may add to the list
+              retry_pending = false;
+              if (c->h_counter[RB_RETRY]) {
+                retry_launch();
+                if (hipMemcpyAsync(c->h_counter + RB_WAVE_N, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
+              }
             }
+            cnt = c->h_counter[RB_WAVE_N];
           }
-          cnt = c->h_counter[14];
+          c->st.n_wave = cnt;
+          pt_launch_knn_wave<Rec>(c->gp, src, cell_start, nullptr, nullptr, 0xFFFFFFFFu, tg, cnt, k, bnd, idx_dev, d2_dev, list, list_n, c->stream,
+                                  wattr, wnattr, wmode, wrgb, wnrm);
+          wave_blended = true;
+          return;
         }
-        c->st.n_wave = cnt;
-        pt_launch_knn_wave<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, nullptr, nullptr, 0xFFFFFFFFu, tg, cnt, k, bnd, idx_dev, d2_dev, list, list_n, c->stream,
-                                 wattr, wnattr, wmode, wrgb, wnrm);
-        wave_blended = true;
+        (void)hipMemsetAsync(heavy, 0, m, c->stream);
+        pt_launch_mark_near<Rec>(c->gp, tg, list, list_n, m, (const uint8_t*)c->near_node.p, heavy, c->stream);
+        if (wave_lists()) { wave_pair(tg, bnd, true); wave_blended = true; }
         return;
       }
-      (void)hipMemsetAsync(heavy, 0, m, c->stream);
-      pt_launch_mark_near<RecF>(c->gp, tg, list, list_n, m, (const uint8_t*)c->near_node.p, heavy, c->stream);
-      if (wave_lists()) {
-        pt_launch_knn_wave<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, nullptr, nullptr, 0xFFFFFFFFu, tg, c->h_counter[12], k, bnd, idx_dev, d2_dev,
-                                 hlist, hcnt, c->stream, wattr, wnattr, wmode, wrgb, wnrm);
-        pt_launch_knn_wave<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold,
-                                 tg, c->h_counter[13], k, bnd, idx_dev, d2_dev, hlist + c->h_counter[12], hcnt + 1, c->stream, wattr, wnattr, wmode, wrgb, wnrm);
-        wave_blended = true;                                // (every marked target is on one of the two lists)
-      }
-      return;
-    }
-    if (wave) (void)hipMemsetAsync(heavy, 0, m, c->stream);
-    if (hier) pt_launch_knn_hier<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
-    else pt_launch_knn<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
-    if (wave && wave_lists()) {                             // plain variant for the first list, descending variant for the second
-      pt_launch_knn_wave<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, nullptr, nullptr, 0xFFFFFFFFu, tg, c->h_counter[12], k, bnd, idx_dev, d2_dev,
-                               hlist, hcnt, c->stream);
-      pt_launch_knn_wave<RecF>(c->gp, (const RecF*)c->rec.p, (const uint32_t*)c->cell_start.p, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold,
-                               tg, c->h_counter[13], k, bnd, idx_dev, d2_dev, hlist + c->h_counter[12], hcnt + 1, c->stream);
-    }
-  };
-  auto group_f64 = [&](const RecD* tg, const double* bnd, const uint32_t* list, const uint32_t* list_n) {
-    if (wave && c->wave_min <= 1) {
-      // every target gets a wave (measured on the clustered generator: the group kernel loses to it even on the sparse targets there,
-      // and marking 50 M targets costs it 70 ms): no group kernel at all.  Without refined cells the list is the input list;
-      // with them, a one-load-per-target pass marks who needs the descending variant.
-      if (!hier) {
-        uint32_t cnt = m;
-        if (list) {                                           // a device-side list (what the tile kernel left over): its length sizes the launch
-          if (hipMemcpyAsync(c->h_counter + 14, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
-          if (retry_pending) {                                // the second-chance blocks' count came with it: their launch may add to the list
-            retry_pending = false;
-            if (c->h_counter[5]) {
-              retry_launch();
-              if (hipMemcpyAsync(c->h_counter + 14, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
-            }
-          }
-          cnt = c->h_counter[14];
-        }
-        c->st.n_wave = cnt;
-        pt_launch_knn_wave<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, nullptr, nullptr, 0xFFFFFFFFu, tg, cnt, k, bnd, idx_dev, d2_dev, list, list_n, c->stream,
-                                 wattr, wnattr, wmode, wrgb, wnrm);
-        wave_blended = true;
-        return;
-      }
-      (void)hipMemsetAsync(heavy, 0, m, c->stream);
-      pt_launch_mark_near<RecD>(c->gp, tg, list, list_n, m, (const uint8_t*)c->near_node.p, heavy, c->stream);
-      if (wave_lists()) {
-        pt_launch_knn_wave<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, nullptr, nullptr, 0xFFFFFFFFu, tg, c->h_counter[12], k, bnd, idx_dev, d2_dev,
-                                 hlist, hcnt, c->stream, wattr, wnattr, wmode, wrgb, wnrm);
-        pt_launch_knn_wave<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold,
-                                 tg, c->h_counter[13], k, bnd, idx_dev, d2_dev, hlist + c->h_counter[12], hcnt + 1, c->stream, wattr, wnattr, wmode, wrgb, wnrm);
-        wave_blended = true;                                // (every marked target is on one of the two lists)
-      }
-      return;
-    }
-    if (wave) (void)hipMemsetAsync(heavy, 0, m, c->stream);
-    if (hier) pt_launch_knn_hier<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
-    else pt_launch_knn<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
-    if (wave && wave_lists()) {
-      pt_launch_knn_wave<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, nullptr, nullptr, 0xFFFFFFFFu, tg, c->h_counter[12], k, bnd, idx_dev, d2_dev,
-                               hlist, hcnt, c->stream);
-      pt_launch_knn_wave<RecD>(c->gp, (const RecD*)c->rec.p, (const uint32_t*)c->cell_start.p, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold,
-                               tg, c->h_counter[13], k, bnd, idx_dev, d2_dev, hlist + c->h_counter[12], hcnt + 1, c->stream);
-    }
-  };
-  if (ttype == PT_F32) {
-    const float* x = (const float*)txyz;
+      if (wave) (void)hipMemsetAsync(heavy, 0, m, c->stream);
+      if (hier) pt_launch_knn_hier<Rec>(c->gp, src, cell_start, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
+      else pt_launch_knn<Rec>(c->gp, src, cell_start, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
+      if (wave && wave_lists()) wave_pair(tg, bnd, false);
+    };
     // targets only need to be grouped by block (tile kernel) -- the cell-level pass is skipped
-    const RecF* tsorted = pt_launch_grid_sort<float, RecF>(c->gp, x, x + m, x + 2 * (size_t)m, nullptr, m, (RecF*)c->trec.p, (RecF*)c->trec_tmp.p, nullptr, c->ttb, false, c->stream);
+    const Rec* tsorted = pt_launch_grid_sort(c->gp, x, x + m, x + 2 * (size_t)m, nullptr, m, (Rec*)c->trec.p, (Rec*)c->trec_tmp.p, nullptr, c->ttb, false, c->stream);
     if (!tsorted) return fail(c, PT_ERR_HIP, "target binning: a launch of the sort failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     if (use_tile) {
-      { int r = tile_launches((const RecF*)c->rec.p, tsorted, nullptr, nullptr, todo_n); if (r != PT_OK) return r; }
-      group_f32(tsorted, bound2_dev, (const uint32_t*)c->todo.p, todo_n);       // (what the tile kernel left over keeps its bound, if it came with one)
+      int r;
+      if constexpr (std::is_same<Rec, RecF>::value) r = tile_launches(src, tsorted, nullptr, nullptr, todo_n);
+      else r = tile_launches((const RecF*)c->rec32.p, nullptr, src, tsorted, todo_n);
+      if (r != PT_OK) return r;
+      group(tsorted, bound2_dev, (const uint32_t*)c->todo.p, todo_n);       // (what the tile kernel left over keeps its bound, if it came with one)
       if (br && !wave_blended)   // the targets the tile kernel handed over get their blend from the lists the group kernel just wrote
-        pt_launch_blend_list<RecF>((const uint32_t*)c->todo.p, todo_n, m, tsorted, idx_dev, d2_dev, k, br->mode, (const Attr*)c->attr.p,
-                                   (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 4, todo_n, 4, hipMemcpyDeviceToHost, c->stream));
+        pt_launch_blend_list<Rec>((const uint32_t*)c->todo.p, todo_n, m, tsorted, idx_dev, d2_dev, k, br->mode, (const Attr*)c->attr.p,
+                                  (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_TODO, todo_n, 4, hipMemcpyDeviceToHost, c->stream));
     } else {
-      group_f32(tsorted, bound2_dev, nullptr, nullptr);
+      group(tsorted, bound2_dev, nullptr, nullptr);
       if (br && !wave_blended) pt_launch_blend(idx_dev, d2_dev, m, k, br->mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
     }
-  } else {
-    const double* x = (const double*)txyz;
-    const RecD* tsorted = pt_launch_grid_sort<double, RecD>(c->gp, x, x + m, x + 2 * (size_t)m, nullptr, m, (RecD*)c->trec.p, (RecD*)c->trec_tmp.p, nullptr, c->ttb, false, c->stream);
-    if (!tsorted) return fail(c, PT_ERR_HIP, "target binning: a launch of the sort failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    if (use_tile) {
-      { int r = tile_launches((const RecF*)c->rec32.p, nullptr, (const RecD*)c->rec.p, tsorted, todo_n); if (r != PT_OK) return r; }
-      group_f64(tsorted, bound2_dev, (const uint32_t*)c->todo.p, todo_n);       // (what the tile kernel left over keeps its bound, if it came with one)
-      if (br && !wave_blended)
-        pt_launch_blend_list<RecD>((const uint32_t*)c->todo.p, todo_n, m, tsorted, idx_dev, d2_dev, k, br->mode, (const Attr*)c->attr.p,
-                                   (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 4, todo_n, 4, hipMemcpyDeviceToHost, c->stream));
-    } else {
-      group_f64(tsorted, bound2_dev, nullptr, nullptr);
-      if (br && !wave_blended) pt_launch_blend(idx_dev, d2_dev, m, k, br->mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
-    }
-  }
-  if (c->local_mode && m) pt_launch_ids_to_global(idx_dev, (size_t)m * (size_t)k, (const uint32_t*)c->in_gidx.p, c->stream);      // positions in the slab -> global indices (every blend above used the positions)
+    return PT_OK;
+  });
+  if (typed != PT_OK) return typed;
+  if (c->local_ids() && m) pt_launch_ids_to_global(idx_dev, (size_t)m * (size_t)k, (const uint32_t*)c->in_gidx.p, c->stream);      // positions in the slab -> global indices (every blend above used the positions)
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
   HIPCHK(c, hipGetLastError());
   c->st.n_target = m;
@@ -903,7 +917,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
     c->st.ms_query = b;
     c->st.ms_kernel[6] = a;
     c->st.ms_kernel[7] = b;
-    c->st.n_leftover = use_tile ? c->h_counter[4] : 0;
+    c->st.n_leftover = use_tile ? c->h_counter[RB_TODO] : 0;
   }
   return PT_OK;
 }
@@ -941,6 +955,71 @@ int load_transient(pt_ctx* c, const void* xyz, int& xyz_type, uint64_t m, int on
   return PT_OK;
 }
 
+// a query of the transient targets (x_xyz) whose lists go to host memory, staged in q_idx / q_d2
+int query_transient_to_host(pt_ctx* c, int type, uint64_t m, int k, uint32_t* idx, double* d2_or_null) {
+  RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
+  if (d2_or_null) RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
+  { int r = run_query(c, c->x_xyz.p, type, m, k, nullptr, (uint32_t*)c->q_idx.p, d2_or_null ? (double*)c->q_d2.p : nullptr); if (r) return r; }
+  if (m) {
+    HIPCHK(c, hipMemcpyAsync(idx, c->q_idx.p, m * k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d2_or_null) HIPCHK(c, hipMemcpyAsync(d2_or_null, c->q_d2.p, m * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return PT_OK;
+}
+
+// the attribute table of the resident cloud: n_total records, packed from caller arrays (host or device)
+int upload_attributes(pt_ctx* c, const uint8_t* rgb, const float* nrm, uint64_t n_total, int on_device) {
+  HIPCHK(c, hipSetDevice(c->device));
+  RES(c, c->attr, std::max<uint64_t>(n_total, 1) * sizeof(Attr));
+  const uint8_t* drgb = rgb;
+  const float* dnrm = nrm;
+  if (!on_device) {
+    RES(c, c->misc, std::max<uint64_t>(n_total, 1) * 15);
+    uint8_t* base = (uint8_t*)c->misc.p;
+    if (nrm) { int r = copy_in(c, base, nrm, n_total * 12, 0); if (r) return r; dnrm = (const float*)base; }
+    if (rgb) { int r = copy_in(c, base + n_total * 12, rgb, n_total * 3, 0); if (r) return r; drgb = base + n_total * 12; }
+  }
+  pt_launch_pack_attr(drgb, dnrm, (uint32_t)n_total, (Attr*)c->attr.p, c->stream);
+  c->n_total = n_total;
+  c->has_attr = true; c->posattr_valid = false;
+  return finish(c);
+}
+
+// blends read the attribute table by the ids in finished lists (global indices): a local-id slab's table is indexed by position, found in
+// the slab's ascending gidx.  An entry that names another slab's point (a row the exchange completed) cannot be blended from here --
+// pt_exchange_merge_* re-blends those rows itself
+int attr_ids(pt_ctx* c, const uint32_t*& idx_dev, uint64_t m, int k) {
+  if (!c->attr_local()) return PT_OK;
+  RES(c, c->l_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
+  pt_launch_ids_to_local(idx_dev, (size_t)m * k, (const uint32_t*)c->in_gidx.p, (uint32_t)c->n, (uint32_t*)c->l_idx.p, c->stream);
+  idx_dev = (const uint32_t*)c->l_idx.p;
+  return PT_OK;
+}
+
+// the blends of host lists: idx and w (distances or weights, may be null) into q_idx / q_d2, `dev` -- the device blend into b_rgb /
+// b_nrm -- with a host wait, the results back
+template <class Dev>
+int blend_host(pt_ctx* c, const uint32_t* idx, const double* w, uint64_t m, int k, float* rgb_out, float* nrm_out, Dev&& dev) {
+  HIPCHK(c, hipSetDevice(c->device));
+  RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
+  RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
+  RES(c, c->b_rgb, std::max<uint64_t>(m, 1) * 12);
+  RES(c, c->b_nrm, std::max<uint64_t>(m, 1) * 12);
+  { int r = copy_in(c, c->q_idx.p, idx, m * k * sizeof(uint32_t), 0); if (r) return r; }
+  if (w) { int r = copy_in(c, c->q_d2.p, w, m * k * sizeof(double), 0); if (r) return r; }
+  const int sync_save = c->sync;
+  c->sync = 1;
+  const int r = dev();
+  c->sync = sync_save;
+  if (r != PT_OK) return r;
+  if (m) {
+    if (rgb_out) HIPCHK(c, hipMemcpy(rgb_out, c->b_rgb.p, m * 12, hipMemcpyDeviceToHost));
+    if (nrm_out) HIPCHK(c, hipMemcpy(nrm_out, c->b_nrm.p, m * 12, hipMemcpyDeviceToHost));
+  }
+  return PT_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -966,11 +1045,11 @@ int pt_ctx_create(pt_ctx** out, const int* device_ids, int n_devices) {
     if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
   for (auto& e : c->xev)
     if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
-  if (hipHostMalloc((void**)&c->h_bbox, 10 * sizeof(uint64_t)) != hipSuccess || hipHostMalloc((void**)&c->h_counter, 64) != hipSuccess) {
+  if (hipHostMalloc((void**)&c->h_bbox, BB_WORDS * sizeof(uint64_t)) != hipSuccess || hipHostMalloc((void**)&c->h_counter, RB_WORDS * sizeof(uint32_t)) != hipSuccess) {
     delete c;
     return PT_ERR_HIP;
   }
-  if (reserve(c, c->bbox6, 64) != PT_OK || reserve(c, c->counter, 64) != PT_OK) { delete c; return PT_ERR_NOMEM; }
+  if (reserve(c, c->bbox6, 64) != PT_OK || reserve(c, c->counter, RB_WORDS * sizeof(uint32_t)) != PT_OK) { delete c; return PT_ERR_NOMEM; }
   *out = c;
   return PT_OK;
 }
@@ -1004,7 +1083,7 @@ int pt_set_stream(pt_ctx* c, void* hip_stream) {
 
 int pt_set_param(pt_ctx* c, const char* name, double value) {
   if (!c || !name) return PT_ERR_ARG;
-  c->hint_h = 0.0;                     // (whatever changes, the next build searches its cell size afresh)
+  c->learned.hint_h = 0.0;             // (whatever changes, the next build searches its cell size afresh)
   if (!strcmp(name, "rho")) { if (!(value >= 1e-4 && value <= 4096)) return fail(c, PT_ERR_ARG, "rho out of range"); c->rho = value; return PT_OK; }
   if (!strcmp(name, "k_hint")) {
     // cell density for the k the caller is going to ask for: ring 1 (3x3x3 cells) must usually contain the k nearest
@@ -1022,19 +1101,19 @@ int pt_set_param(pt_ctx* c, const char* name, double value) {
   if (!strcmp(name, "dup_runs")) { c->dup_runs = value != 0; return PT_OK; }
   if (!strcmp(name, "local_ids")) { c->want_local_ids = value != 0; return PT_OK; }      // before pt_build_soa_indexed: see pt_set_attributes_local
   if (!strcmp(name, "tile_contrast")) { c->tile_contrast = (int)value; return PT_OK; }
-  if (!strcmp(name, "grid_hint")) { c->grid_hint = value != 0; if (!c->grid_hint) c->hint_h = 0.0; return PT_OK; }
+  if (!strcmp(name, "grid_hint")) { c->grid_hint = value != 0; if (!c->grid_hint) c->learned.hint_h = 0.0; return PT_OK; }
   if (!strcmp(name, "refine_cells_per_point")) { if (!(value > 0 && value <= 1e6)) return fail(c, PT_ERR_ARG, "refine_cells_per_point out of range"); c->refine_cpp = value; return PT_OK; }
   if (!strcmp(name, "refine_macros")) { if (!(value >= 1 && value <= PT_MAX_MACROS)) return fail(c, PT_ERR_ARG, "refine_macros out of range"); c->refine_macros = (int)value; return PT_OK; }
   if (!strcmp(name, "wave_force")) { c->wave_force = value != 0; return PT_OK; }
   if (!strcmp(name, "wave_min")) { if (!(value >= 0 && value <= 4e9)) return fail(c, PT_ERR_ARG, "wave_min out of range"); c->wave_min = (uint32_t)value; return PT_OK; }
   if (!strcmp(name, "refine_threshold")) { if (!(value >= 0 && value <= 1e9)) return fail(c, PT_ERR_ARG, "refine_threshold out of range"); c->refine_threshold = value; return PT_OK; }
-  if (!strcmp(name, "pool2")) { c->pool2 = value != 0; c->pool2_ok = true; return PT_OK; }    // pass 2 without its histogram on clouds found uniform (1, default) or never (0)
+  if (!strcmp(name, "pool2")) { c->pool2 = value != 0; c->learned.pool2_ok = true; return PT_OK; }    // pass 2 without its histogram on clouds found uniform (1, default) or never (0)
   if (!strcmp(name, "stream_bounds")) { c->stream_bounds = value != 0; return PT_OK; }
   // "forget": the next build of the resident cloud decides everything a FIRST build decides (sampled bounding box, pooled passes, uniformity
   // sample, cell size) -- what bench.py times as its cold step, buffers already allocated
-  if (!strcmp(name, "forget")) { if (value != 0) { c->bbox_guess_ok = true; c->pool_ok = true; c->pool2_ok = true; c->uniform_seen = false; c->uniform_known = false; c->hint_h = 0.0; } return PT_OK; }
+  if (!strcmp(name, "forget")) { if (value != 0) c->learned = Learned{}; return PT_OK; }
   if (!strcmp(name, "presort_refine")) { c->presort_refine = value != 0; return PT_OK; }
-  if (!strcmp(name, "pool_min_points")) { c->pool_min_points = value < 0 ? 0 : (uint64_t)value; c->pool_ok = true; return PT_OK; }   // pooled pass 1 from this size up (0: never)
+  if (!strcmp(name, "pool_min_points")) { c->pool_min_points = value < 0 ? 0 : (uint64_t)value; c->learned.pool_ok = true; return PT_OK; }   // pooled pass 1 from this size up (0: never)
   if (!strcmp(name, "guess_min_points")) { c->guess_min_points = value < 1 ? 1 : (uint64_t)value; return PT_OK; }   // sampled-bbox builds from this size up   // 0 group kernel only, 1 auto, 2 small tiles, 3 large tiles
   if (!strcmp(name, "own_stream")) { if (value != 0) c->stream = c->own_stream; return PT_OK; }
   return fail(c, PT_ERR_ARG, "unknown parameter '%s'", name);
@@ -1070,7 +1149,7 @@ int pt_build_aos(pt_ctx* c, const pt_point* cloud, uint64_t n) {
   { int r = copy_in(c, c->aos_stage.p, cloud, n * sizeof(pt_point), 0); if (r) return r; }
   double* x = (double*)c->in_xyz.p;
   pt_launch_aos_split(c->aos_stage.p, (uint32_t)n, x, x + n, x + 2 * n, (Attr*)c->attr.p, c->stream);
-  c->src_type = PT_F64; c->n = n; c->n_total = n; c->has_gidx = false; c->local_mode = false; c->attr_local = false; c->has_attr = true; c->built = false; c->posattr_valid = false; c->bbox_guess_ok = true; c->pool_ok = true; c->pool2_ok = true; c->uniform_seen = false; c->uniform_known = false; c->hint_h = 0.0; c->in_half = false; c->xyz32_valid = false;
+  adopt_cloud(c, PT_F64, n, n, IdMode::whole, false, true);
   return rebuild(c);
 }
 
@@ -1091,66 +1170,37 @@ int pt_build_soa_indexed(pt_ctx* c, const void* xyz, int xyz_type, const uint32_
     RES(c, c->in_gidx, std::max<uint64_t>(n, 1) * sizeof(uint32_t));
     { int r = copy_in(c, c->in_gidx.p, gidx, n * sizeof(uint32_t), on_device); if (r) return r; }
   }
-  c->src_type = xyz_type; c->n = n; c->has_gidx = gidx != nullptr; c->built = false;
-  c->local_mode = false;
+  bool ascending = false;
   if (gidx && c->want_local_ids) {
-    uint32_t* flag = (uint32_t*)c->counter.p + 1;
+    uint32_t* flag = (uint32_t*)c->counter.p + RB_ASCENDING;
     HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
     pt_launch_ascending((const uint32_t*)c->in_gidx.p, (uint32_t)n, flag, c->stream);
-    HIPCHK(c, hipMemcpyAsync(c->h_counter + 1, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_ASCENDING, flag, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_counter[1]) return fail(c, PT_ERR_ARG, "local_ids: the slab's global indices must be strictly ascending (positions then order like indices)");
-    c->local_mode = true; c->synth_total = 0;
-    c->has_attr = false; c->attr_local = false;
+    ascending = c->h_counter[RB_ASCENDING] == 0;
   }
-  if (!gidx) { c->n_total = n; c->has_attr = false; c->attr_local = false; }
-  c->posattr_valid = false; c->bbox_guess_ok = true; c->pool_ok = true; c->pool2_ok = true; c->uniform_seen = false; c->uniform_known = false; c->hint_h = 0.0; c->in_half = keep_half; c->xyz32_valid = false;
+  // a slab keeps the size of the attribute table it is indexed into (a whole cloud: its own); a refused local-id slab stays unbuilt
+  adopt_cloud(c, xyz_type, n, gidx ? c->n_total : n, !gidx ? IdMode::whole : (ascending ? IdMode::slab_local : IdMode::slab_global), keep_half, false);
+  if (gidx && c->want_local_ids && !ascending) return fail(c, PT_ERR_ARG, "local_ids: the slab's global indices must be strictly ascending (positions then order like indices)");
   return rebuild(c);
 }
 
 int pt_set_attributes_local(pt_ctx* c, const uint8_t* rgb, const float* nrm, int on_device) {
   if (!c) return PT_ERR_ARG;
-  if (!c->local_mode) return fail(c, PT_ERR_STATE, "pt_set_attributes_local: build the slab with pt_set_param(\"local_ids\", 1) and ascending global indices first");
-  const uint64_t n = c->n;
-  HIPCHK(c, hipSetDevice(c->device));
-  RES(c, c->attr, std::max<uint64_t>(n, 1) * sizeof(Attr));
-  const uint8_t* drgb = rgb;
-  const float* dnrm = nrm;
-  if (!on_device) {
-    RES(c, c->misc, std::max<uint64_t>(n, 1) * 15);
-    uint8_t* base = (uint8_t*)c->misc.p;
-    if (nrm) { int r = copy_in(c, base, nrm, n * 12, 0); if (r) return r; dnrm = (const float*)base; }
-    if (rgb) { int r = copy_in(c, base + n * 12, rgb, n * 3, 0); if (r) return r; drgb = base + n * 12; }
-  }
-  pt_launch_pack_attr(drgb, dnrm, (uint32_t)n, (Attr*)c->attr.p, c->stream);
-  c->n_total = n;                      // the table's size: the slab's own points
-  c->has_attr = true; c->attr_local = true; c->posattr_valid = false;
-  return finish(c);
+  if (!c->local_ids()) return fail(c, PT_ERR_STATE, "pt_set_attributes_local: build the slab with pt_set_param(\"local_ids\", 1) and ascending global indices first");
+  return upload_attributes(c, rgb, nrm, c->n, on_device);          // the table's size: the slab's own points
 }
 
 int pt_set_attributes(pt_ctx* c, const uint8_t* rgb, const float* nrm, uint64_t n_total, int on_device) {
   if (!c) return PT_ERR_ARG;
-  if (c->local_mode) return fail(c, PT_ERR_STATE, "this slab keeps local ids: its attribute table is pt_set_attributes_local's (its own points' records)");
+  if (c->local_ids()) return fail(c, PT_ERR_STATE, "this slab keeps local ids: its attribute table is pt_set_attributes_local's (its own points' records)");
   { int r = check_n(c, n_total, "n_total"); if (r) return r; }
-  HIPCHK(c, hipSetDevice(c->device));
-  RES(c, c->attr, std::max<uint64_t>(n_total, 1) * sizeof(Attr));
-  const uint8_t* drgb = rgb;
-  const float* dnrm = nrm;
-  if (!on_device) {
-    RES(c, c->misc, std::max<uint64_t>(n_total, 1) * 15);
-    uint8_t* base = (uint8_t*)c->misc.p;
-    if (nrm) { int r = copy_in(c, base, nrm, n_total * 12, 0); if (r) return r; dnrm = (const float*)base; }
-    if (rgb) { int r = copy_in(c, base + n_total * 12, rgb, n_total * 3, 0); if (r) return r; drgb = base + n_total * 12; }
-  }
-  pt_launch_pack_attr(drgb, dnrm, (uint32_t)n_total, (Attr*)c->attr.p, c->stream);
-  c->n_total = n_total;
-  c->has_attr = true; c->posattr_valid = false;
-  return finish(c);
+  return upload_attributes(c, rgb, nrm, n_total, on_device);
 }
 
 int pt_set_attributes_range(pt_ctx* c, uint64_t first, uint64_t count, const uint8_t* rgb, const float* nrm, uint64_t n_total) {
   if (!c) return PT_ERR_ARG;
-  if (c->local_mode) return fail(c, PT_ERR_STATE, "this slab keeps local ids: its attribute table is pt_set_attributes_local's (its own points' records)");
+  if (c->local_ids()) return fail(c, PT_ERR_STATE, "this slab keeps local ids: its attribute table is pt_set_attributes_local's (its own points' records)");
   { int r = check_n(c, n_total, "n_total"); if (r) return r; }
   if (first > n_total || count > n_total - first) return fail(c, PT_ERR_ARG, "pt_set_attributes_range: [first, first + count) outside the table of n_total records");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1203,25 +1253,27 @@ int pt_build_synth(pt_ctx* c, uint64_t n_total, uint64_t seed, int dist, int xyz
     HIPCHK(c, hipMemsetAsync(wg_cnt + nwg, 0, 4, c->stream));
     pt_launch_synth_xyz<float>(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, nullptr, nullptr, nullptr, nullptr, nullptr, 0, f16, dist, n_total, 0, c->stream, wg_cnt, nullptr);
     pt_launch_scan_u32(wg_cnt, wg_off, nwg + 1, scan_tmp, c->stream);
-    HIPCHK(c, hipMemcpyAsync(c->h_counter, wg_off + nwg, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_SLAB_N, wg_off + nwg, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    n = *c->h_counter;
+    n = c->h_counter[RB_SLAB_N];
     RES(c, c->in_gidx, std::max<uint64_t>(n, 1) * sizeof(uint32_t));
   } else if (slab) {   // counting pass
-    HIPCHK(c, hipMemsetAsync(c->counter.p, 0, 4, c->stream));
-    pt_launch_synth_xyz<float>(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, nullptr, nullptr, nullptr, nullptr, (uint32_t*)c->counter.p, 0, f16, dist, n_total, 0, c->stream);
-    HIPCHK(c, hipMemcpyAsync(c->h_counter, c->counter.p, 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t* cnt = (uint32_t*)c->counter.p + RB_SLAB_N;
+    HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
+    pt_launch_synth_xyz<float>(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, nullptr, nullptr, nullptr, nullptr, cnt, 0, f16, dist, n_total, 0, c->stream);
+    HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_SLAB_N, cnt, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    n = *c->h_counter;
+    n = c->h_counter[RB_SLAB_N];
     RES(c, c->in_gidx, std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-    HIPCHK(c, hipMemsetAsync(c->counter.p, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
   }
   const bool keep_half = f16 != 0;
   RES(c, c->in_xyz, std::max<uint64_t>(n, 1) * 3 * (keep_half ? sizeof(__half) : tsize(xyz_type)));
   uint32_t* g = slab ? (uint32_t*)c->in_gidx.p : nullptr;
-  if (keep_half) { __half* x = (__half*)c->in_xyz.p; pt_launch_synth_xyz<__half>(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, x, x + n, x + 2 * n, g, (uint32_t*)c->counter.p, (uint32_t)n, 1, dist, n_total, 0, c->stream, nullptr, ordered ? wg_off : nullptr); }
-  else if (xyz_type == PT_F32) { float* x = (float*)c->in_xyz.p; pt_launch_synth_xyz<float>(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, x, x + n, x + 2 * n, g, (uint32_t*)c->counter.p, (uint32_t)n, f16, dist, n_total, 0, c->stream, nullptr, ordered ? wg_off : nullptr); }
-  else { double* x = (double*)c->in_xyz.p; pt_launch_synth_xyz<double>(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, x, x + n, x + 2 * n, g, (uint32_t*)c->counter.p, (uint32_t)n, f16, dist, n_total, 0, c->stream, nullptr, ordered ? wg_off : nullptr); }
+  by_coords(xyz_type, keep_half, c->in_xyz.p, [&](auto x, auto) {
+    pt_launch_synth_xyz(seed, 0, (uint32_t)n_total, slab_axis, slab_lo, slab_hi, x, x + n, x + 2 * n, g, (uint32_t*)c->counter.p + RB_SLAB_N, (uint32_t)n,
+                        keep_half ? 1 : f16, dist, n_total, 0, c->stream, nullptr, ordered ? wg_off : nullptr);     // round_f16: 1 on the fp16 branch, f16 (0) on the others
+  });
   if (ordered) {                                   // the slab's own records only: 16 n bytes instead of 16 n_total
     RES(c, c->attr, std::max<uint64_t>(n, 1) * sizeof(Attr));
     pt_launch_synth_attr(seed, (uint32_t)n, (Attr*)c->attr.p, c->stream, (const uint32_t*)c->in_gidx.p);
@@ -1229,7 +1281,7 @@ int pt_build_synth(pt_ctx* c, uint64_t n_total, uint64_t seed, int dist, int xyz
     RES(c, c->attr, std::max<uint64_t>(n_total, 1) * sizeof(Attr));
     pt_launch_synth_attr(seed, (uint32_t)n_total, (Attr*)c->attr.p, c->stream);
   }
-  c->src_type = xyz_type; c->n = n; c->n_total = ordered ? n : n_total; c->synth_total = n_total; c->has_gidx = slab; c->local_mode = ordered; c->attr_local = ordered; c->has_attr = true; c->built = false; c->posattr_valid = false; c->bbox_guess_ok = true; c->pool_ok = true; c->pool2_ok = true; c->uniform_seen = false; c->uniform_known = false; c->hint_h = 0.0; c->in_half = keep_half; c->xyz32_valid = false;
+  adopt_cloud(c, xyz_type, n, ordered ? n : n_total, ordered ? IdMode::slab_local : (slab ? IdMode::slab_global : IdMode::whole), keep_half, true, n_total);
   return rebuild(c);
 }
 
@@ -1251,19 +1303,22 @@ int pt_targets_synth(pt_ctx* c, uint64_t m_total, uint64_t seed, int dist, int x
   HIPCHK(c, hipSetDevice(c->device));
   uint64_t m = m_total;
   const bool slab = slab_axis >= 0;
+  const uint64_t src_total = (c->local_ids() && c->synth_total) ? c->synth_total : c->n_total;     // the clustered generator's source count
+  uint32_t* cnt = (uint32_t*)c->counter.p + RB_SLAB_N;
   if (slab) {
-    HIPCHK(c, hipMemsetAsync(c->counter.p, 0, 4, c->stream));
-    pt_launch_synth_xyz<float>(seed, 1, (uint32_t)m_total, slab_axis, slab_lo, slab_hi, nullptr, nullptr, nullptr, nullptr, (uint32_t*)c->counter.p, 0, f16, dist, (c->local_mode && c->synth_total) ? c->synth_total : c->n_total, m_total, c->stream);
-    HIPCHK(c, hipMemcpyAsync(c->h_counter, c->counter.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
+    pt_launch_synth_xyz<float>(seed, 1, (uint32_t)m_total, slab_axis, slab_lo, slab_hi, nullptr, nullptr, nullptr, nullptr, cnt, 0, f16, dist, src_total, m_total, c->stream);
+    HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_SLAB_N, cnt, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    m = *c->h_counter;
-    HIPCHK(c, hipMemsetAsync(c->counter.p, 0, 4, c->stream));
+    m = c->h_counter[RB_SLAB_N];
+    HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
   }
   RES(c, c->t_gidx, std::max<uint64_t>(m, 1) * sizeof(uint32_t));
   RES(c, c->t_xyz, std::max<uint64_t>(m, 1) * 3 * tsize(xyz_type));
   uint32_t* g = (uint32_t*)c->t_gidx.p;
-  if (xyz_type == PT_F32) { float* x = (float*)c->t_xyz.p; pt_launch_synth_xyz<float>(seed, 1, (uint32_t)m_total, slab_axis, slab_lo, slab_hi, x, x + m, x + 2 * m, g, (uint32_t*)c->counter.p, (uint32_t)m, f16, dist, (c->local_mode && c->synth_total) ? c->synth_total : c->n_total, m_total, c->stream); }
-  else { double* x = (double*)c->t_xyz.p; pt_launch_synth_xyz<double>(seed, 1, (uint32_t)m_total, slab_axis, slab_lo, slab_hi, x, x + m, x + 2 * m, g, (uint32_t*)c->counter.p, (uint32_t)m, f16, dist, (c->local_mode && c->synth_total) ? c->synth_total : c->n_total, m_total, c->stream); }
+  by_type(xyz_type, c->t_xyz.p, [&](auto x, auto) {
+    pt_launch_synth_xyz(seed, 1, (uint32_t)m_total, slab_axis, slab_lo, slab_hi, x, x + m, x + 2 * m, g, cnt, (uint32_t)m, f16, dist, src_total, m_total, c->stream);
+  });
   c->tgt_type = xyz_type; c->m = m; c->t_has_gidx = true;
   return finish(c);
 }
@@ -1364,15 +1419,7 @@ int pt_query_soa(pt_ctx* c, const void* xyz, int xyz_type, uint64_t m, int k, in
   if (m && !idx) return fail(c, PT_ERR_ARG, "idx output is null");
   { int r = load_transient(c, xyz, xyz_type, m, on_device); if (r) return r; }
   if (on_device) return run_query(c, c->x_xyz.p, xyz_type, m, k, nullptr, idx, d2_or_null);
-  RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
-  if (d2_or_null) RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
-  { int r = run_query(c, c->x_xyz.p, xyz_type, m, k, nullptr, (uint32_t*)c->q_idx.p, d2_or_null ? (double*)c->q_d2.p : nullptr); if (r) return r; }
-  if (m) {
-    HIPCHK(c, hipMemcpyAsync(idx, c->q_idx.p, m * k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (d2_or_null) HIPCHK(c, hipMemcpyAsync(d2_or_null, c->q_d2.p, m * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return PT_OK;
+  return query_transient_to_host(c, xyz_type, m, k, idx, d2_or_null);
 }
 
 int pt_query_aos(pt_ctx* c, const pt_point* targets, uint64_t m, int k, uint32_t* idx, double* d2_or_null) {
@@ -1386,15 +1433,7 @@ int pt_query_aos(pt_ctx* c, const pt_point* targets, uint64_t m, int k, uint32_t
   { int r = copy_in(c, c->aos_stage.p, targets, m * sizeof(pt_point), 0); if (r) return r; }
   double* x = (double*)c->x_xyz.p;
   pt_launch_aos_split(c->aos_stage.p, (uint32_t)m, x, x + m, x + 2 * m, nullptr, c->stream);
-  RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
-  if (d2_or_null) RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
-  { int r = run_query(c, c->x_xyz.p, PT_F64, m, k, nullptr, (uint32_t*)c->q_idx.p, d2_or_null ? (double*)c->q_d2.p : nullptr); if (r) return r; }
-  if (m) {
-    HIPCHK(c, hipMemcpyAsync(idx, c->q_idx.p, m * k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (d2_or_null) HIPCHK(c, hipMemcpyAsync(d2_or_null, c->q_d2.p, m * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return PT_OK;
+  return query_transient_to_host(c, PT_F64, m, k, idx, d2_or_null);
 }
 
 int pt_query_bounded_dev(pt_ctx* c, const void* xyz_dev, int xyz_type, const double* bound2_dev, uint64_t m, int k, uint32_t* idx_dev,
@@ -1416,13 +1455,7 @@ int pt_blend_dev(pt_ctx* c, const uint32_t* idx_dev, const double* d2_dev_or_nul
   if (m && !idx_dev) return fail(c, PT_ERR_ARG, "idx is null");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  if (c->attr_local) {
-    // the table holds this slab's points by POSITION: the lists' global indices are looked up in the slab's ascending gidx; an entry that
-    // names another slab's point (a row the exchange completed) cannot be blended from here -- pt_exchange_merge_* re-blends those rows itself
-    RES(c, c->l_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
-    pt_launch_ids_to_local(idx_dev, (size_t)m * k, (const uint32_t*)c->in_gidx.p, (uint32_t)c->n, (uint32_t*)c->l_idx.p, c->stream);
-    idx_dev = (const uint32_t*)c->l_idx.p;
-  }
+  { int r = attr_ids(c, idx_dev, m, k); if (r) return r; }
   pt_launch_blend(idx_dev, d2_dev_or_null, (uint32_t)m, k, mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb_out_dev, nrm_out_dev, c->stream);
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
@@ -1439,23 +1472,9 @@ int pt_blend(pt_ctx* c, const uint32_t* idx, const double* d2_or_null, uint64_t 
   if (!c) return PT_ERR_ARG;
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k out of range");
   if (m && !idx) return fail(c, PT_ERR_ARG, "idx is null");
-  HIPCHK(c, hipSetDevice(c->device));
-  RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
-  RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
-  RES(c, c->b_rgb, std::max<uint64_t>(m, 1) * 12);
-  RES(c, c->b_nrm, std::max<uint64_t>(m, 1) * 12);
-  { int r = copy_in(c, c->q_idx.p, idx, m * k * sizeof(uint32_t), 0); if (r) return r; }
-  if (d2_or_null) { int r = copy_in(c, c->q_d2.p, d2_or_null, m * k * sizeof(double), 0); if (r) return r; }
-  const int sync_save = c->sync;
-  c->sync = 1;
-  int r = pt_blend_dev(c, (const uint32_t*)c->q_idx.p, d2_or_null ? (const double*)c->q_d2.p : nullptr, m, k, mode, (float*)c->b_rgb.p, (float*)c->b_nrm.p);
-  c->sync = sync_save;
-  if (r != PT_OK) return r;
-  if (m) {
-    if (rgb_out) HIPCHK(c, hipMemcpy(rgb_out, c->b_rgb.p, m * 12, hipMemcpyDeviceToHost));
-    if (nrm_out) HIPCHK(c, hipMemcpy(nrm_out, c->b_nrm.p, m * 12, hipMemcpyDeviceToHost));
-  }
-  return PT_OK;
+  return blend_host(c, idx, d2_or_null, m, k, rgb_out, nrm_out, [&]() {
+    return pt_blend_dev(c, (const uint32_t*)c->q_idx.p, d2_or_null ? (const double*)c->q_d2.p : nullptr, m, k, mode, (float*)c->b_rgb.p, (float*)c->b_nrm.p);
+  });
 }
 
 int pt_blend_weighted_dev(pt_ctx* c, const uint32_t* idx_dev, const double* w_dev, uint64_t m, int k, float* rgb_out_dev, float* nrm_out_dev) {
@@ -1464,11 +1483,7 @@ int pt_blend_weighted_dev(pt_ctx* c, const uint32_t* idx_dev, const double* w_de
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k out of range");
   if (m && (!idx_dev || !w_dev)) return fail(c, PT_ERR_ARG, "null argument");
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->attr_local) {                                       // (as pt_blend_dev: global indices -> positions in this slab's table)
-    RES(c, c->l_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
-    pt_launch_ids_to_local(idx_dev, (size_t)m * k, (const uint32_t*)c->in_gidx.p, (uint32_t)c->n, (uint32_t*)c->l_idx.p, c->stream);
-    idx_dev = (const uint32_t*)c->l_idx.p;
-  }
+  { int r = attr_ids(c, idx_dev, m, k); if (r) return r; }
   pt_launch_blend_weighted(idx_dev, w_dev, (uint32_t)m, k, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb_out_dev, nrm_out_dev, c->stream);
   HIPCHK(c, hipGetLastError());
   return finish(c);
@@ -1478,29 +1493,15 @@ int pt_blend_weighted(pt_ctx* c, const uint32_t* idx, const double* w, uint64_t 
   if (!c) return PT_ERR_ARG;
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k out of range");
   if (m && (!idx || !w)) return fail(c, PT_ERR_ARG, "null argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
-  RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
-  RES(c, c->b_rgb, std::max<uint64_t>(m, 1) * 12);
-  RES(c, c->b_nrm, std::max<uint64_t>(m, 1) * 12);
-  { int r = copy_in(c, c->q_idx.p, idx, m * k * sizeof(uint32_t), 0); if (r) return r; }
-  { int r = copy_in(c, c->q_d2.p, w, m * k * sizeof(double), 0); if (r) return r; }
-  const int sync_save = c->sync;
-  c->sync = 1;
-  int r = pt_blend_weighted_dev(c, (const uint32_t*)c->q_idx.p, (const double*)c->q_d2.p, m, k, (float*)c->b_rgb.p, (float*)c->b_nrm.p);
-  c->sync = sync_save;
-  if (r != PT_OK) return r;
-  if (m) {
-    if (rgb_out) HIPCHK(c, hipMemcpy(rgb_out, c->b_rgb.p, m * 12, hipMemcpyDeviceToHost));
-    if (nrm_out) HIPCHK(c, hipMemcpy(nrm_out, c->b_nrm.p, m * 12, hipMemcpyDeviceToHost));
-  }
-  return PT_OK;
+  return blend_host(c, idx, w, m, k, rgb_out, nrm_out, [&]() {
+    return pt_blend_weighted_dev(c, (const uint32_t*)c->q_idx.p, (const double*)c->q_d2.p, m, k, (float*)c->b_rgb.p, (float*)c->b_nrm.p);
+  });
 }
 
 int pt_pca_normals_dev(pt_ctx* c, const uint32_t* idx_dev, uint64_t m, int k, float* nrm_out_dev) {
   if (!c) return PT_ERR_ARG;
   if (c->src_type < 0) return fail(c, PT_ERR_STATE, "no source cloud resident");
-  if (c->has_gidx) return fail(c, PT_ERR_UNSUPPORTED, "PCA normals need the whole cloud resident (not a slab)");
+  if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "PCA normals need the whole cloud resident (not a slab)");
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k out of range");
   if (m && (!idx_dev || !nrm_out_dev)) return fail(c, PT_ERR_ARG, "null argument");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1572,8 +1573,9 @@ int pt_slab_need_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, const dou
   RES(c, c->bounds, 65 * sizeof(double));
   HIPCHK(c, hipMemcpyAsync(c->bounds.p, slab_bounds, (size_t)(g + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (xyz_type == PT_F32) { const float* x = (const float*)tgt_xyz_dev; pt_launch_slab_need<float>(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, need_dev, c->stream); }
-  else { const double* x = (const double*)tgt_xyz_dev; pt_launch_slab_need<double>(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, need_dev, c->stream); }
+  by_type(xyz_type, tgt_xyz_dev, [&](auto x, auto) {
+    pt_launch_slab_need(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, need_dev, c->stream);
+  });
   HIPCHK(c, hipGetLastError());
   return finish(c);
 }
@@ -1587,16 +1589,17 @@ int pt_pack_requests_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, const
   { int r = check_n(c, m, "m"); if (r) return r; }
   HIPCHK(c, hipSetDevice(c->device));
   RES(c, c->bounds, 65 * sizeof(double));
-  uint32_t* cnt = (uint32_t*)c->counter.p + 6;
+  uint32_t* cnt = (uint32_t*)c->counter.p + RB_COUNT;
   HIPCHK(c, hipMemcpyAsync(c->bounds.p, slab_bounds, (size_t)(g + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));       // (slab_bounds is the caller's host memory)
-  if (xyz_type == PT_F32) { const float* x = (const float*)tgt_xyz_dev; pt_launch_request_pack<float>(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, cnt, sel_out_dev, pkt_out_dev, c->stream); }
-  else { const double* x = (const double*)tgt_xyz_dev; pt_launch_request_pack<double>(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, cnt, sel_out_dev, pkt_out_dev, c->stream); }
+  by_type(xyz_type, tgt_xyz_dev, [&](auto x, auto) {
+    pt_launch_request_pack(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, cnt, sel_out_dev, pkt_out_dev, c->stream);
+  });
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_counter + 6, cnt, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_COUNT, cnt, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *count_out = c->h_counter[6];
+  *count_out = c->h_counter[RB_COUNT];
   return PT_OK;
 }
 
@@ -1620,7 +1623,7 @@ int pt_upload_begin(pt_ctx* c, uint64_t n, int xyz_type, int with_attributes) {
     RES(c, c->attr, std::max<uint64_t>(n, 1) * sizeof(Attr));
   }
   c->up_n = n; c->up_type = xyz_type; c->up_attr = with_attributes ? 1 : 0;
-  c->built = false; c->src_type = -1;            // nothing usable until pt_upload_end
+  adopt_cloud(c, -1, 0, 0, IdMode::whole, false, false);      // nothing usable until pt_upload_end
   return PT_OK;
 }
 
@@ -1650,8 +1653,7 @@ int pt_upload_end(pt_ctx* c) {
   const uint64_t n = c->up_n;
   if (c->up_attr) pt_launch_pack_attr((const uint8_t*)c->up_rgb.p, (const float*)c->up_nrm.p, (uint32_t)n, (Attr*)c->attr.p, c->stream);
   HIPCHK(c, hipStreamSynchronize(c->stream));                                // the caller's buffers are free again
-  c->src_type = c->up_type; c->n = n; c->n_total = n; c->has_gidx = false; c->local_mode = false; c->attr_local = false; c->has_attr = c->up_attr != 0; c->built = false;
-  c->posattr_valid = false; c->bbox_guess_ok = true; c->pool_ok = true; c->pool2_ok = true; c->uniform_seen = false; c->uniform_known = false; c->hint_h = 0.0; c->in_half = false; c->xyz32_valid = false;
+  adopt_cloud(c, c->up_type, n, n, IdMode::whole, false, c->up_attr != 0);
   c->up_type = -1;
   release(c, c->up_rgb); release(c, c->up_nrm);
   return rebuild(c);
@@ -1678,10 +1680,8 @@ int pt_stream_query(pt_ctx* c, const void* xyz, int xyz_type, uint64_t n, uint64
   hipEvent_t copied[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
   const int sync_save = c->sync;
   DevBuf keep_in = c->in_xyz;                       // the context's own input buffer: put back at the end (the chunks live in `stage`)
-  const bool keep_half = c->in_half;
   auto cleanup = [&]() {
     c->in_xyz = keep_in;
-    c->in_half = keep_half; c->xyz32_valid = false;
     c->sync = sync_save;
     c->tile_bounds = false;
     DevBuf* all[] = {&best_i[0], &best_i[1], &best_d[0], &best_d[1], &ci, &cd, &stage[0], &stage[1], &sbound, &sfirst};
@@ -1721,25 +1721,24 @@ int pt_stream_query(pt_ctx* c, const void* xyz, int xyz_type, uint64_t n, uint64
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     std::vector<double> boxes((size_t)nchunks * 6), margins((size_t)nchunks, 0.0);
-    uint32_t* cnt_dev = (uint32_t*)c->counter.p + 6;
+    uint32_t* cnt_dev = (uint32_t*)c->counter.p + RB_COUNT;
     // one (chunk, sweep): stage[b] holds chunk ch -- exact bounding box (forward sweep; remembered for the backward one), the bounds the
     // targets bring and how many of them reach the box at all, then build + search + merge unless nobody does
     auto adopt = [&](uint64_t ch, int b) {
       const uint64_t f0 = ch * chunk_points, cnt = std::min<uint64_t>(chunk_points, n - f0);
       c->in_xyz = stage[b];
-      c->src_type = xyz_type; c->n = cnt; c->n_total = cnt; c->has_gidx = false; c->local_mode = false; c->attr_local = false; c->has_attr = false; c->built = false;
-      c->posattr_valid = false; c->bbox_guess_ok = true; c->pool_ok = true; c->pool2_ok = true; c->uniform_seen = false; c->uniform_known = false; c->hint_h = 0.0; c->in_half = false; c->xyz32_valid = false;
+      adopt_cloud(c, xyz_type, cnt, cnt, IdMode::whole, false, false);
     };
     auto bounds_and_reach = [&](uint64_t ch, int backward, uint32_t& reach) -> int {
       const double* mn = &boxes[(size_t)ch * 6];
       HIPCHK(c, hipMemsetAsync(cnt_dev, 0, 4, c->stream));
-      if (xyz_type == PT_F32) pt_launch_stream_sweep<float>((const float*)c->t_xyz.p, (const unsigned long long*)best_i[cur].p, (const double*)best_d[cur].p, (uint32_t)m, k, (uint32_t)ch,
-                                                            backward, (uint32_t*)sfirst.p, mn, mn + 3, margins[(size_t)ch], (double*)sbound.p, cnt_dev, c->stream);
-      else pt_launch_stream_sweep<double>((const double*)c->t_xyz.p, (const unsigned long long*)best_i[cur].p, (const double*)best_d[cur].p, (uint32_t)m, k, (uint32_t)ch,
-                                          backward, (uint32_t*)sfirst.p, mn, mn + 3, margins[(size_t)ch], (double*)sbound.p, cnt_dev, c->stream);
-      HIPCHK(c, hipMemcpyAsync(c->h_counter + 6, cnt_dev, 4, hipMemcpyDeviceToHost, c->stream));
+      by_type(xyz_type, (const void*)c->t_xyz.p, [&](auto x, auto) {
+        pt_launch_stream_sweep(x, (const unsigned long long*)best_i[cur].p, (const double*)best_d[cur].p, (uint32_t)m, k, (uint32_t)ch, backward, (uint32_t*)sfirst.p,
+                               mn, mn + 3, margins[(size_t)ch], (double*)sbound.p, cnt_dev, c->stream);
+      });
+      HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_COUNT, cnt_dev, 4, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      reach = c->h_counter[6];
+      reach = c->h_counter[RB_COUNT];
       return PT_OK;
     };
     auto search_and_merge = [&](uint64_t ch, int b) -> int {
@@ -1812,7 +1811,7 @@ int pt_stream_query(pt_ctx* c, const void* xyz, int xyz_type, uint64_t n, uint64
   c->st.stream_skipped = (int32_t)std::min<uint64_t>(skipped, 0x7FFFFFFF);
   c->st.stream_revisited = (int32_t)std::min<uint64_t>(revisited, 0x7FFFFFFF);
   // the chunks are gone with the stage buffers: no source cloud is resident any more (a later query needs a pt_build_* first)
-  c->n = 0; c->n_total = 0; c->built = false; c->src_type = -1; c->has_attr = false;
+  adopt_cloud(c, -1, 0, 0, IdMode::whole, false, false);
   return r;
 }
 
@@ -1885,8 +1884,9 @@ int xa_count(pt_ctx* c, const XArgs& A, const double* bounds) {
   RES(c, c->x_counts, 64 * sizeof(uint32_t));
   HIPCHK(c, hipMemcpyAsync(c->x_bounds.p, bounds, (size_t)(A.g + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->x_counts.p, 0, 64 * sizeof(uint32_t), c->stream));
-  if (A.type == PT_F32) { const float* x = (const float*)A.xyz; pt_launch_xreq<float>(false, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, A.g, A.me, (uint32_t*)c->x_counts.p, nullptr, nullptr, nullptr, nullptr, c->stream); }
-  else { const double* x = (const double*)A.xyz; pt_launch_xreq<double>(false, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, A.g, A.me, (uint32_t*)c->x_counts.p, nullptr, nullptr, nullptr, nullptr, c->stream); }
+  by_type(A.type, A.xyz, [&](auto x, auto) {
+    pt_launch_xreq(false, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, A.g, A.me, (uint32_t*)c->x_counts.p, nullptr, nullptr, nullptr, nullptr, c->stream);
+  });
   HIPCHK(c, hipGetLastError());
   return PT_OK;
 }
@@ -1902,7 +1902,7 @@ int xb_fill(pt_ctx* c, const XArgs& A, const uint32_t* matrix) {
   RES(c, c->x_rreq, std::max<size_t>(R, 1) * 32);
   RES(c, c->x_back_i, std::max<size_t>(S, 1) * (size_t)A.k * 4); RES(c, c->x_back_d, std::max<size_t>(S, 1) * (size_t)A.k * 8);
   RES(c, c->x_ans_i, std::max<size_t>(R, 1) * (size_t)A.k * 4); RES(c, c->x_ans_d, std::max<size_t>(R, 1) * (size_t)A.k * 8);
-  if (c->attr_local) { RES(c, c->x_ans_a, std::max<size_t>(R, 1) * (size_t)A.k * sizeof(Attr)); RES(c, c->x_back_a, std::max<size_t>(S, 1) * (size_t)A.k * sizeof(Attr)); }
+  if (c->attr_local()) { RES(c, c->x_ans_a, std::max<size_t>(R, 1) * (size_t)A.k * sizeof(Attr)); RES(c, c->x_back_a, std::max<size_t>(S, 1) * (size_t)A.k * sizeof(Attr)); }
   uint32_t* off = (uint32_t*)c->x_off.p;
   uint32_t* cursor = off + 65;
   // the offsets travel from PINNED memory, so the copy needs no host wait; the event says when the staging words may be rewritten
@@ -1913,10 +1913,10 @@ int xb_fill(pt_ctx* c, const XArgs& A, const uint32_t* matrix) {
   HIPCHK(c, hipMemcpyAsync(off, c->h_xoff, (size_t)(g + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipEventRecord(c->xoff_ev, c->stream));
   HIPCHK(c, hipMemsetAsync(cursor, 0, 65 * sizeof(uint32_t), c->stream));
-  if (S) {
-    if (A.type == PT_F32) { const float* x = (const float*)A.xyz; pt_launch_xreq<float>(true, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, g, me, nullptr, off, cursor, (double*)c->x_req.p, (uint32_t*)c->x_row.p, c->stream); }
-    else { const double* x = (const double*)A.xyz; pt_launch_xreq<double>(true, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, g, me, nullptr, off, cursor, (double*)c->x_req.p, (uint32_t*)c->x_row.p, c->stream); }
-  }
+  if (S)
+    by_type(A.type, A.xyz, [&](auto x, auto) {
+      pt_launch_xreq(true, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, g, me, nullptr, off, cursor, (double*)c->x_req.p, (uint32_t*)c->x_row.p, c->stream);
+    });
   HIPCHK(c, hipGetLastError());
   return PT_OK;
 }
@@ -1925,11 +1925,10 @@ int xc_answer(pt_ctx* c, const XArgs& A) {
   const uint32_t R = c->x_roff[(size_t)A.g];
   if (!R) return PT_OK;
   RES(c, c->x_rxyz, (size_t)R * 3 * tsize(A.type)); RES(c, c->x_rbound, (size_t)R * 8);
-  if (A.type == PT_F32) pt_launch_xunpack<float>((const double*)c->x_rreq.p, R, (float*)c->x_rxyz.p, (double*)c->x_rbound.p, c->stream);
-  else pt_launch_xunpack<double>((const double*)c->x_rreq.p, R, (double*)c->x_rxyz.p, (double*)c->x_rbound.p, c->stream);
+  by_type(A.type, c->x_rxyz.p, [&](auto x, auto) { pt_launch_xunpack((const double*)c->x_rreq.p, R, x, (double*)c->x_rbound.p, c->stream); });
   { int r = run_query(c, c->x_rxyz.p, A.type, R, A.k, (const double*)c->x_rbound.p, (uint32_t*)c->x_ans_i.p, (double*)c->x_ans_d.p); if (r) return r; }
   // attribute table sharded with the slabs: the candidates' records ride along (they are this slab's points: found by position in its ascending gidx)
-  if (c->attr_local && c->has_attr)
+  if (c->attr_local())
     pt_launch_xgather_attr((const uint32_t*)c->x_ans_i.p, (size_t)R * (size_t)A.k, (const uint32_t*)c->in_gidx.p, (uint32_t)c->n, (const Attr*)c->attr.p, (Attr*)c->x_ans_a.p, c->stream);
   return PT_OK;
 }
@@ -1938,7 +1937,7 @@ int xd_merge(pt_ctx* c, const XArgs& A, int blend_mode, float* rgb, float* nrm) 
   const uint32_t S = c->x_soff[(size_t)A.g];
   if (!S) return PT_OK;
   const bool reblend = blend_mode >= 0 && (rgb || nrm) && c->has_attr;
-  const bool sharded = reblend && c->attr_local;        // the table holds this slab's points only: the merge carries the candidates' records along
+  const bool sharded = reblend && c->attr_local();        // the table holds this slab's points only: the merge carries the candidates' records along
   uint8_t* flags = nullptr;
   if (reblend) {
     RES(c, c->x_flags, std::max<size_t>(A.m, 1)); RES(c, c->x_rows, (std::max<size_t>(A.m, 1) + 4) * 4);
@@ -2060,7 +2059,7 @@ int pt_exchange_merge_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, uint
       const size_t ro = (size_t)c->x_roff[(size_t)p] * k, rc = (size_t)c->x_recv[(size_t)p] * k, so = (size_t)c->x_soff[(size_t)p] * k, sc = (size_t)c->x_send[(size_t)p] * k;
       if (rc) { NCCLGRP(gerr, gwhat, rccl()->Send((const uint32_t*)c->x_ans_i.p + ro, rc, ncclUint32, p, comm, c->stream)); NCCLGRP(gerr, gwhat, rccl()->Send((const double*)c->x_ans_d.p + ro, rc, ncclFloat64, p, comm, c->stream)); }
       if (sc) { NCCLGRP(gerr, gwhat, rccl()->Recv((uint32_t*)c->x_back_i.p + so, sc, ncclUint32, p, comm, c->stream)); NCCLGRP(gerr, gwhat, rccl()->Recv((double*)c->x_back_d.p + so, sc, ncclFloat64, p, comm, c->stream)); }
-      if (c->attr_local) {      // (every rank of a job runs the same mode: the candidates' 16-byte records as four words each)
+      if (c->attr_local()) {    // (every rank of a job runs the same mode: the candidates' 16-byte records as four words each)
         if (rc) NCCLGRP(gerr, gwhat, rccl()->Send((const uint32_t*)c->x_ans_a.p + ro * 4, rc * 4, ncclUint32, p, comm, c->stream));
         if (sc) NCCLGRP(gerr, gwhat, rccl()->Recv((uint32_t*)c->x_back_a.p + so * 4, sc * 4, ncclUint32, p, comm, c->stream));
       }
@@ -2077,7 +2076,7 @@ int pt_exchange_merge_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, uint
   if (st) {
     const uint64_t S = c->x_soff[(size_t)g], R = c->x_roff[(size_t)g];
     st->crossing = S; st->answered = R;
-    const uint64_t cand = c->attr_local ? 28 : 12;        // (index + distance, + the attribute record when the table is sharded)
+    const uint64_t cand = c->attr_local() ? 28 : 12;        // (index + distance, + the attribute record when the table is sharded)
     st->bytes_sent = S * 32 + R * (uint64_t)k * cand; st->bytes_received = R * 32 + S * (uint64_t)k * cand;
   }
   if (c->sync || st) {
@@ -2163,7 +2162,7 @@ int pt_exchange_merge_local(pt_ctx* const* ctxs, int g, const void* const* tgt_x
         const size_t ro = (size_t)a->x_roff[(size_t)p] * k, cnt = (size_t)a->x_recv[(size_t)p] * k, so = (size_t)b->x_soff[(size_t)r] * k;
         HIPCHK(a, hipMemcpyAsync((uint32_t*)b->x_back_i.p + so, (const uint32_t*)a->x_ans_i.p + ro, cnt * 4, hipMemcpyDeviceToDevice, a->stream));
         HIPCHK(a, hipMemcpyAsync((double*)b->x_back_d.p + so, (const double*)a->x_ans_d.p + ro, cnt * 8, hipMemcpyDeviceToDevice, a->stream));
-        if (a->attr_local && b->attr_local) HIPCHK(a, hipMemcpyAsync((Attr*)b->x_back_a.p + so, (const Attr*)a->x_ans_a.p + ro, cnt * sizeof(Attr), hipMemcpyDeviceToDevice, a->stream));
+        if (a->attr_local() && b->attr_local()) HIPCHK(a, hipMemcpyAsync((Attr*)b->x_back_a.p + so, (const Attr*)a->x_ans_a.p + ro, cnt * sizeof(Attr), hipMemcpyDeviceToDevice, a->stream));
       }
     { int e = all_sync(); if (e) return e; }
     for (int r = 0; r < g; ++r) { int e = xd_merge(ctxs[r], A[(size_t)r], blend_mode, rgb_dev ? rgb_dev[r] : nullptr, nrm_dev ? nrm_dev[r] : nullptr); if (e) return e; }
@@ -2179,7 +2178,7 @@ int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const
                     int resolution, int pad_ksize, uint8_t* bgra_out) {
   if (!c) return PT_ERR_ARG;
   if (c->src_type != PT_F32 && c->src_type != PT_F64) return fail(c, PT_ERR_STATE, "no source cloud resident (call a pt_build_* first)");
-  if (c->has_gidx) return fail(c, PT_ERR_UNSUPPORTED, "the texture bake needs the whole cloud resident (not a slab)");
+  if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "the texture bake needs the whole cloud resident (not a slab)");
   if (!c->has_attr) return fail(c, PT_ERR_STATE, "no attribute table resident (the bake reads the source colours)");
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [1, %d]", k, PT_MAX_K);
   if (resolution < 1 || resolution > 32768) return fail(c, PT_ERR_ARG, "resolution out of range [1, 32768]");

@@ -1504,7 +1504,8 @@ def test_native_exchange_on_logical_slabs(pkg, oracle, g, k, f64, sharded):
 def test_local_id_slab_matches_the_global_id_slab(pkg, oracle):
     """A slab whose records carry positions instead of global indices ("local_ids"): the same lists -- ties among duplicates resolved by the
     global index, which ascending indices make the positional order -- the fused blend from the slab's own attribute records within 1e-5 of
-    the replicated table's, on the tile kernel and on the wave kernel; indices that do not ascend are refused."""
+    the replicated table's, on the tile kernel and on the wave kernel; indices that do not ascend are refused.  A context that leaves local-id
+    mode drops the slab's own table: a blend is refused until the global table is uploaded, and then matches."""
     import torch
     rng = np.random.default_rng(55)
     n_all, n, m, k = 300_000, 120_000, 5000, 16
@@ -1535,6 +1536,20 @@ def test_local_id_slab_matches_the_global_id_slab(pkg, oracle):
             p.blend_dev(idx, d2, m, k, pkg.BLEND_INV_D2, c2, n2)              # a finished list (global indices) against the local table
             torch.cuda.synchronize()
             assert np.abs(c2.cpu().numpy() - rc).max() / 255.0 <= TOL and np.abs(n2.cpu().numpy() - rn).max() <= TOL
+    with pkg.PointsTransfer(device=0, k_hint=k) as p:
+        p.set_param("local_ids", 1)
+        p.build(src, gidx=sel)
+        p.set_attributes_local(rgb[sel], nrm[sel])
+        p.set_param("local_ids", 0)
+        p.build(src, gidx=sel)                                                # the same slab with global ids: the local table is gone
+        idx = torch.from_numpy(wi.view(np.int32)).cuda(); d2 = torch.from_numpy(wd).cuda()
+        c2 = torch.empty((m, 3), dtype=torch.float32, device="cuda"); n2 = torch.empty_like(c2)
+        with pytest.raises(pkg.PtError):
+            p.blend_dev(idx, d2, m, k, pkg.BLEND_INV_D2, c2, n2)
+        p.set_attributes(rgb, nrm)
+        p.blend_dev(idx, d2, m, k, pkg.BLEND_INV_D2, c2, n2)
+        torch.cuda.synchronize()
+        assert np.abs(c2.cpu().numpy() - rc).max() / 255.0 <= TOL and np.abs(n2.cpu().numpy() - rn).max() <= TOL
     with pkg.PointsTransfer(device=0, k_hint=k) as p:
         p.set_param("local_ids", 1)
         bad = sel.copy(); bad[[10, 11]] = bad[[11, 10]]
