@@ -131,6 +131,9 @@ struct pt_ctx {
   bool attr_local() const { return ids == IdMode::slab_local && has_attr; }     // the table holds this slab's points by position
   bool want_local_ids = false; // "local_ids": the next pt_build_soa_indexed / pt_build_synth of a slab builds it in local-id mode (ascending gidx)
   uint64_t guess_min_points = 8u << 20;   // clouds at least this large lay their grid out from a sampled bounding box
+  double max_dist = INFINITY;  // "max_dist": neighbours farther than this are not returned (+inf: off) ...
+  double cap2 = INFINITY;      // ... and its square, computed once in double: a point is in reach iff d2 <= cap2
+  bool capped() const { return cap2 < INFINITY; }
   bool stream_bounds = true;   // pt_stream_query: later chunks are searched under the targets' current k-th distances and skipped when out of reach ("stream_bounds", a measurement switch)
   bool tile_bounds = false;    // run_query: bounds come with every target of the set (the tile kernel's bounded variant may take them)
   bool pool2 = true;           // pass 2 without its histogram on clouds found uniform: allowed ("pool2")
@@ -182,6 +185,7 @@ struct pt_ctx {
 
   // scratch
   DevBuf bbox6, counter, q_idx, q_d2, b_rgb, b_nrm, aos_stage, misc, bounds, todo, retry, heavy, tlist;
+  DevBuf cap_bnd;              // capped queries: the per-target bounds min(bound2[t], cap2) the group / hier / wave kernels read
   uint64_t* h_bbox = nullptr;   // pinned
   uint32_t* h_counter = nullptr;
 
@@ -735,8 +739,18 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
   // EVERY target of a block-sorted set (pt_stream_query from its second chunk on): then the tile kernel's bounded variant takes them
   // (round 4: fp64 clouds and k in 25..32 as well -- ADVICE r3: since every chunk of a streamed cloud brings bounds, those went to the
   //  8-lane group kernel in EVERY chunk, the first, unbounded one included)
-  const bool tile_bounded = bound2_dev && c->tile_bounds && !br && k <= PT_TILE_MAX_K;
-  const bool use_tile = c->tile && (!contrast || (c->tile_contrast && k <= 24)) && (!bound2_dev || tile_bounded) && m && k <= PT_TILE_MAX_K && h2_ok && (ttype == PT_F32 || c->rec32_valid);
+  // A max_dist cap (c->cap2 < +inf) reaches the tile kernel as one uniform bound, fused blend included; per-target bounds that come with
+  // it still go where they went without the cap.  Everything else (the tile kernel's leftovers, the group / hier / wave kernels) reads
+  // per-target bounds: cap_bnd[t] = min(bound2[t], cap2).
+  const bool capped = c->capped();
+  const bool tile_bounded = capped ? (!bound2_dev || (c->tile_bounds && !br)) && k <= PT_TILE_MAX_K : bound2_dev && c->tile_bounds && !br && k <= PT_TILE_MAX_K;
+  const bool use_tile = c->tile && (!contrast || (c->tile_contrast && k <= 24)) && (!(bound2_dev || capped) || tile_bounded) && m && k <= PT_TILE_MAX_K && h2_ok && (ttype == PT_F32 || c->rec32_valid);
+  const double* bnd_all = bound2_dev;                   // what the group / hier / wave kernels get
+  if (capped && m) {
+    RES(c, c->cap_bnd, (size_t)m * sizeof(double));
+    pt_launch_cap_bounds(bound2_dev, m, c->cap2, (double*)c->cap_bnd.p, c->stream);
+    bnd_all = (const double*)c->cap_bnd.p;
+  }
   // The tile kernel over all blocks (+ the large geometry for the blocks the small one had to pass on); what it cannot
   // settle is on the todo list afterwards.  fp64 clouds: the LDS image is the fp32 shadow of the sorted records, the exact
   // 32-byte records are fetched for the few candidates that reach the ranking pass.
@@ -775,12 +789,12 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
     }
     pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
                        tile_small, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr, blist, nlist,
-                       second_chance ? (uint32_t*)c->retry.p : nullptr, retry_n, src64, tgt64, c->e_src, c->stream, bound2_dev);
+                       second_chance ? (uint32_t*)c->retry.p : nullptr, retry_n, src64, tgt64, c->e_src, c->stream, bound2_dev, c->cap2);
     if (second_chance) {
       retry_launch = [=]() {
         pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
                            0, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr,
-                           (const uint32_t*)c->retry.p, c->h_counter[RB_RETRY], nullptr, nullptr, src64, tgt64, c->e_src, c->stream, bound2_dev);
+                           (const uint32_t*)c->retry.p, c->h_counter[RB_RETRY], nullptr, nullptr, src64, tgt64, c->e_src, c->stream, bound2_dev, c->cap2);
       };
       HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_RETRY, retry_n, 4, hipMemcpyDeviceToHost, c->stream));
       // (round 4) when the leftover pass reads the todo list's length anyway -- one wave per leftover target -- the two counts share that
@@ -814,7 +828,8 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
   }
   c->st.n_wave = 0;
   bool wave_blended = false;       // the wave kernel answered every target this call was about AND blended it: no blend pass afterwards
-  const Attr* wattr = br ? (const Attr*)c->attr.p : nullptr;
+  // (capped: the wave kernel does not blend -- its fused epilogue writes empty rows; the keep-empty blend pass below takes its targets)
+  const Attr* wattr = br && !capped ? (const Attr*)c->attr.p : nullptr;
   const uint32_t wnattr = (uint32_t)c->n_total;
   const int wmode = br ? br->mode : 0;
   float* wrgb = br ? br->rgb_out : nullptr;
@@ -867,12 +882,12 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
           c->st.n_wave = cnt;
           pt_launch_knn_wave<Rec>(c->gp, src, cell_start, nullptr, nullptr, 0xFFFFFFFFu, tg, cnt, k, bnd, idx_dev, d2_dev, list, list_n, c->stream,
                                   wattr, wnattr, wmode, wrgb, wnrm);
-          wave_blended = true;
+          wave_blended = wattr != nullptr;
           return;
         }
         (void)hipMemsetAsync(heavy, 0, m, c->stream);
         pt_launch_mark_near<Rec>(c->gp, tg, list, list_n, m, (const uint8_t*)c->near_node.p, heavy, c->stream);
-        if (wave_lists()) { wave_pair(tg, bnd, true); wave_blended = true; }
+        if (wave_lists()) { wave_pair(tg, bnd, wattr != nullptr); wave_blended = wattr != nullptr; }
         return;
       }
       if (wave) (void)hipMemsetAsync(heavy, 0, m, c->stream);
@@ -889,14 +904,14 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       if constexpr (std::is_same<Rec, RecF>::value) r = tile_launches(src, tsorted, nullptr, nullptr, todo_n);
       else r = tile_launches((const RecF*)c->rec32.p, nullptr, src, tsorted, todo_n);
       if (r != PT_OK) return r;
-      group(tsorted, bound2_dev, (const uint32_t*)c->todo.p, todo_n);       // (what the tile kernel left over keeps its bound, if it came with one)
+      group(tsorted, bnd_all, (const uint32_t*)c->todo.p, todo_n);       // (what the tile kernel left over keeps its bound, if it came with one)
       if (br && !wave_blended)   // the targets the tile kernel handed over get their blend from the lists the group kernel just wrote
         pt_launch_blend_list<Rec>((const uint32_t*)c->todo.p, todo_n, m, tsorted, idx_dev, d2_dev, k, br->mode, (const Attr*)c->attr.p,
-                                  (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
+                                  (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream, capped);
       HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_TODO, todo_n, 4, hipMemcpyDeviceToHost, c->stream));
     } else {
-      group(tsorted, bound2_dev, nullptr, nullptr);
-      if (br && !wave_blended) pt_launch_blend(idx_dev, d2_dev, m, k, br->mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream);
+      group(tsorted, bnd_all, nullptr, nullptr);
+      if (br && !wave_blended) pt_launch_blend(idx_dev, d2_dev, m, k, br->mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream, capped);
     }
     return PT_OK;
   });
@@ -997,10 +1012,18 @@ int attr_ids(pt_ctx* c, const uint32_t*& idx_dev, uint64_t m, int k) {
   return PT_OK;
 }
 
+// capped blends into the staging buffers b_rgb / b_nrm: start them as the caller's host outputs (rows without a neighbour are not written)
+int prefill_blend(pt_ctx* c, uint64_t m, const float* rgb_out, const float* nrm_out) {
+  if (rgb_out) { int r = copy_in(c, c->b_rgb.p, rgb_out, m * 12, 0); if (r) return r; }
+  if (nrm_out) { int r = copy_in(c, c->b_nrm.p, nrm_out, m * 12, 0); if (r) return r; }
+  return PT_OK;
+}
+
 // the blends of host lists: idx and w (distances or weights, may be null) into q_idx / q_d2, `dev` -- the device blend into b_rgb /
 // b_nrm -- with a host wait, the results back
+// prefill (the capped blends): the staging buffers start as the caller's outputs, so that the rows the blend does not write come back unchanged
 template <class Dev>
-int blend_host(pt_ctx* c, const uint32_t* idx, const double* w, uint64_t m, int k, float* rgb_out, float* nrm_out, Dev&& dev) {
+int blend_host(pt_ctx* c, const uint32_t* idx, const double* w, uint64_t m, int k, float* rgb_out, float* nrm_out, Dev&& dev, bool prefill = false) {
   HIPCHK(c, hipSetDevice(c->device));
   RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
   RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
@@ -1008,6 +1031,7 @@ int blend_host(pt_ctx* c, const uint32_t* idx, const double* w, uint64_t m, int 
   RES(c, c->b_nrm, std::max<uint64_t>(m, 1) * 12);
   { int r = copy_in(c, c->q_idx.p, idx, m * k * sizeof(uint32_t), 0); if (r) return r; }
   if (w) { int r = copy_in(c, c->q_d2.p, w, m * k * sizeof(double), 0); if (r) return r; }
+  if (prefill) { int r = prefill_blend(c, m, rgb_out, nrm_out); if (r) return r; }
   const int sync_save = c->sync;
   c->sync = 1;
   const int r = dev();
@@ -1060,7 +1084,7 @@ void pt_ctx_destroy(pt_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf* all[] = {&c->in_xyz, &c->in_gidx, &c->attr, &c->rec, &c->rec_tmp, &c->cell_start, &c->stb_mem, &c->t_xyz, &c->t_gidx, &c->trec,
                    &c->trec_tmp, &c->x_xyz, &c->ttb_mem, &c->bbox6, &c->counter, &c->q_idx, &c->q_d2, &c->b_rgb, &c->b_nrm, &c->aos_stage, &c->misc, &c->bounds, &c->todo, &c->posattr, &c->retry, &c->rec32, &c->up_rgb, &c->up_nrm, &c->x_bounds, &c->x_counts, &c->x_matrix, &c->x_off, &c->x_req, &c->x_row, &c->x_rreq,
-                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx};
+                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd};
   for (DevBuf* b : all) release(c, *b);
   if (c->h_bbox) (void)hipHostFree(c->h_bbox);
   if (c->h_counter) (void)hipHostFree(c->h_counter);
@@ -1083,6 +1107,13 @@ int pt_set_stream(pt_ctx* c, void* hip_stream) {
 
 int pt_set_param(pt_ctx* c, const char* name, double value) {
   if (!c || !name) return PT_ERR_ARG;
+  // "max_dist" (cloud units, >= 0; +inf = off): a query-time setting -- no rebuild, and what the context learned for its next build stays
+  if (!strcmp(name, "max_dist")) {
+    if (!(value >= 0.0)) return fail(c, PT_ERR_ARG, "max_dist must be >= 0 (+inf: off), got %g", value);
+    c->max_dist = value;
+    c->cap2 = value * value;
+    return PT_OK;
+  }
   c->learned.hint_h = 0.0;             // (whatever changes, the next build searches its cell size afresh)
   if (!strcmp(name, "rho")) { if (!(value >= 1e-4 && value <= 4096)) return fail(c, PT_ERR_ARG, "rho out of range"); c->rho = value; return PT_OK; }
   if (!strcmp(name, "k_hint")) {
@@ -1376,6 +1407,7 @@ int pt_query_resident_host(pt_ctx* c, int k, int blend_mode, uint32_t* idx_out, 
   RES(c, c->q_idx, std::max<uint64_t>(m, 1) * k * sizeof(uint32_t));
   RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
   if (blend) { RES(c, c->b_rgb, std::max<uint64_t>(m, 1) * 12); RES(c, c->b_nrm, std::max<uint64_t>(m, 1) * 12); }
+  if (blend && c->capped()) { int r = prefill_blend(c, m, rgb_out, nrm_out); if (r) return r; }
   const BlendReq br{blend_mode, (float*)c->b_rgb.p, (float*)c->b_nrm.p};
   { int r = run_query(c, c->t_xyz.p, c->tgt_type, m, k, nullptr, (uint32_t*)c->q_idx.p, (double*)c->q_d2.p, blend ? &br : nullptr); if (r != PT_OK) return r; }
   if (m) {
@@ -1456,7 +1488,7 @@ int pt_blend_dev(pt_ctx* c, const uint32_t* idx_dev, const double* d2_dev_or_nul
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   { int r = attr_ids(c, idx_dev, m, k); if (r) return r; }
-  pt_launch_blend(idx_dev, d2_dev_or_null, (uint32_t)m, k, mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb_out_dev, nrm_out_dev, c->stream);
+  pt_launch_blend(idx_dev, d2_dev_or_null, (uint32_t)m, k, mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb_out_dev, nrm_out_dev, c->stream, c->capped());
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
   if (c->sync) {
@@ -1474,7 +1506,7 @@ int pt_blend(pt_ctx* c, const uint32_t* idx, const double* d2_or_null, uint64_t 
   if (m && !idx) return fail(c, PT_ERR_ARG, "idx is null");
   return blend_host(c, idx, d2_or_null, m, k, rgb_out, nrm_out, [&]() {
     return pt_blend_dev(c, (const uint32_t*)c->q_idx.p, d2_or_null ? (const double*)c->q_d2.p : nullptr, m, k, mode, (float*)c->b_rgb.p, (float*)c->b_nrm.p);
-  });
+  }, c->capped());
 }
 
 int pt_blend_weighted_dev(pt_ctx* c, const uint32_t* idx_dev, const double* w_dev, uint64_t m, int k, float* rgb_out_dev, float* nrm_out_dev) {
@@ -1574,7 +1606,7 @@ int pt_slab_need_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, const dou
   HIPCHK(c, hipMemcpyAsync(c->bounds.p, slab_bounds, (size_t)(g + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   by_type(xyz_type, tgt_xyz_dev, [&](auto x, auto) {
-    pt_launch_slab_need(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, need_dev, c->stream);
+    pt_launch_slab_need(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, c->cap2, need_dev, c->stream);
   });
   HIPCHK(c, hipGetLastError());
   return finish(c);
@@ -1594,7 +1626,7 @@ int pt_pack_requests_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, const
   HIPCHK(c, hipMemsetAsync(cnt, 0, 4, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));       // (slab_bounds is the caller's host memory)
   by_type(xyz_type, tgt_xyz_dev, [&](auto x, auto) {
-    pt_launch_request_pack(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, cnt, sel_out_dev, pkt_out_dev, c->stream);
+    pt_launch_request_pack(x, x + m, x + 2 * m, d2_dev, (uint32_t)m, k, slab_axis, (const double*)c->bounds.p, g, my_slab, c->cap2, cnt, sel_out_dev, pkt_out_dev, c->stream);
   });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_COUNT, cnt, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1734,7 +1766,7 @@ int pt_stream_query(pt_ctx* c, const void* xyz, int xyz_type, uint64_t n, uint64
       HIPCHK(c, hipMemsetAsync(cnt_dev, 0, 4, c->stream));
       by_type(xyz_type, (const void*)c->t_xyz.p, [&](auto x, auto) {
         pt_launch_stream_sweep(x, (const unsigned long long*)best_i[cur].p, (const double*)best_d[cur].p, (uint32_t)m, k, (uint32_t)ch, backward, (uint32_t*)sfirst.p,
-                               mn, mn + 3, margins[(size_t)ch], (double*)sbound.p, cnt_dev, c->stream);
+                               mn, mn + 3, margins[(size_t)ch], c->cap2, (double*)sbound.p, cnt_dev, c->stream);
       });
       HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_COUNT, cnt_dev, 4, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1885,7 +1917,7 @@ int xa_count(pt_ctx* c, const XArgs& A, const double* bounds) {
   HIPCHK(c, hipMemcpyAsync(c->x_bounds.p, bounds, (size_t)(A.g + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->x_counts.p, 0, 64 * sizeof(uint32_t), c->stream));
   by_type(A.type, A.xyz, [&](auto x, auto) {
-    pt_launch_xreq(false, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, A.g, A.me, (uint32_t*)c->x_counts.p, nullptr, nullptr, nullptr, nullptr, c->stream);
+    pt_launch_xreq(false, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, A.g, A.me, c->cap2, (uint32_t*)c->x_counts.p, nullptr, nullptr, nullptr, nullptr, c->stream);
   });
   HIPCHK(c, hipGetLastError());
   return PT_OK;
@@ -1915,7 +1947,7 @@ int xb_fill(pt_ctx* c, const XArgs& A, const uint32_t* matrix) {
   HIPCHK(c, hipMemsetAsync(cursor, 0, 65 * sizeof(uint32_t), c->stream));
   if (S)
     by_type(A.type, A.xyz, [&](auto x, auto) {
-      pt_launch_xreq(true, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, g, me, nullptr, off, cursor, (double*)c->x_req.p, (uint32_t*)c->x_row.p, c->stream);
+      pt_launch_xreq(true, x, x + A.m, x + 2 * (size_t)A.m, A.d2, A.m, A.k, A.axis, (const double*)c->x_bounds.p, g, me, c->cap2, nullptr, off, cursor, (double*)c->x_req.p, (uint32_t*)c->x_row.p, c->stream);
     });
   HIPCHK(c, hipGetLastError());
   return PT_OK;
@@ -1960,8 +1992,9 @@ int xd_merge(pt_ctx* c, const XArgs& A, int blend_mode, float* rgb, float* nrm) 
     uint32_t* rows_n = rows + std::max<size_t>(A.m, 1);
     HIPCHK(c, hipMemsetAsync(rows_n, 0, 4, c->stream));
     pt_launch_xflag_rows(flags, A.m, rows, rows_n, c->stream);
-    if (sharded) pt_launch_blend_rows_attr(rows, rows_n, std::min<uint32_t>(A.m, S), A.idx, A.d2, (const Attr*)c->x_rattr.p, A.k, blend_mode, rgb, nrm, c->stream);
-    else pt_launch_blend_rows(rows, rows_n, std::min<uint32_t>(A.m, S), A.idx, A.d2, A.k, blend_mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb, nrm, c->stream);
+    if (sharded) pt_launch_blend_rows_attr(rows, rows_n, std::min<uint32_t>(A.m, S), A.idx, A.d2, (const Attr*)c->x_rattr.p, A.k, blend_mode, rgb, nrm, c->stream, c->capped());
+    else pt_launch_blend_rows(rows, rows_n, std::min<uint32_t>(A.m, S), A.idx, A.d2, A.k, blend_mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb, nrm, c->stream,
+                              c->capped());
   }
   HIPCHK(c, hipGetLastError());
   return PT_OK;
@@ -2102,6 +2135,7 @@ int pt_query_exchange_blend(pt_ctx* c, const void* tgt_xyz, int xyz_type, uint64
   RES(c, c->q_d2, std::max<uint64_t>(m, 1) * k * sizeof(double));
   RES(c, c->b_rgb, std::max<uint64_t>(m, 1) * 12);
   RES(c, c->b_nrm, std::max<uint64_t>(m, 1) * 12);
+  if (blend && c->capped()) { int r = prefill_blend(c, m, rgb_out, nrm_out); if (r) return r; }
   const BlendReq br{blend_mode, (float*)c->b_rgb.p, (float*)c->b_nrm.p};
   { int r = run_query(c, c->t_xyz.p, c->tgt_type, m, k, nullptr, (uint32_t*)c->q_idx.p, (double*)c->q_d2.p, blend ? &br : nullptr); if (r) return r; }
   if (c->world > 1) {
@@ -2124,6 +2158,8 @@ int pt_exchange_merge_local(pt_ctx* const* ctxs, int g, const void* const* tgt_x
                             float* const* nrm_dev) {
   if (!ctxs || g < 1 || g > 64 || !tgt_xyz_dev || !m || !idx_dev || !d2_dev) return PT_ERR_ARG;
   for (int r = 0; r < g; ++r) if (!ctxs[r]) return PT_ERR_ARG;
+  for (int r = 1; r < g; ++r)       // every slab answers under the same max_dist (NaN never gets in: pt_set_param refuses it)
+    if (ctxs[r]->cap2 != ctxs[0]->cap2) return fail(ctxs[r], PT_ERR_ARG, "max_dist differs between the contexts (%g here, %g in context 0)", ctxs[r]->max_dist, ctxs[0]->max_dist);
   std::vector<XArgs> A((size_t)g);
   std::vector<int> sync_save((size_t)g);
   for (int r = 0; r < g; ++r) {

@@ -160,10 +160,17 @@ __global__ __launch_bounds__(WG) void pack_attr_kernel(const uint8_t* __restrict
   attr[i] = a;
 }
 
-// gather the k neighbours' 16-B attribute records of target row t and blend them
+// gather the k neighbours' 16-B attribute records of target row t and blend them.  KEEP (the blends of a context with a max_dist cap):
+// a row without any entry is not written, so the caller's values stay
+template <bool KEEP = false>
 __device__ inline void blend_one(const uint32_t* __restrict__ idx, const double* __restrict__ d2, uint32_t t, int k, int mode,
                                  const Attr* __restrict__ attr, uint32_t n_attr, float* __restrict__ rgb_out, float* __restrict__ nrm_out) {
   double wsum = 0.0, c[3] = {0, 0, 0}, nn[3] = {0, 0, 0};
+  if constexpr (KEEP) {
+    bool any = false;
+    for (int j = 0; j < k; ++j) any |= idx[(size_t)t * k + j] != PT_NOIDX_U;
+    if (!any) return;
+  }
   // four neighbours' records in flight per thread (one by one, a thread waited k random-access latencies in a row); the sums keep
   // their order.  A missing neighbour reads record 0 (cached) instead of branching around its load.
   constexpr int GB = 4;
@@ -202,6 +209,13 @@ __global__ __launch_bounds__(WG) void blend_kernel(const uint32_t* __restrict__ 
   if (t >= m) return;
   blend_one(idx, d2, t, k, mode, attr, n_attr, rgb_out, nrm_out);
 }
+__global__ __launch_bounds__(WG) void blend_keep_kernel(const uint32_t* __restrict__ idx, const double* __restrict__ d2, uint32_t m, int k, int mode,
+                                                        const Attr* __restrict__ attr, uint32_t n_attr, float* __restrict__ rgb_out,
+                                                        float* __restrict__ nrm_out) {
+  const uint32_t t = blockIdx.x * WG + threadIdx.x;
+  if (t >= m) return;
+  blend_one<true>(idx, d2, t, k, mode, attr, n_attr, rgb_out, nrm_out);
+}
 
 // the reference's own mix (src/pointsTransfer.cpp:95-97: double weight x int colour, summed left to right in double, stored
 // to a float) for k terms with caller-given weights; no normalisation
@@ -237,6 +251,15 @@ __global__ __launch_bounds__(WG) void blend_list_kernel(const uint32_t* __restri
   if (i >= *list_n) return;
   blend_one(idx, d2, tgt[list[i]].id, k, mode, attr, n_attr, rgb_out, nrm_out);
 }
+template <class Rec>
+__global__ __launch_bounds__(WG) void blend_list_keep_kernel(const uint32_t* __restrict__ list, const uint32_t* __restrict__ list_n,
+                                                             const Rec* __restrict__ tgt, const uint32_t* __restrict__ idx, const double* __restrict__ d2,
+                                                             int k, int mode, const Attr* __restrict__ attr, uint32_t n_attr, float* __restrict__ rgb_out,
+                                                             float* __restrict__ nrm_out) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= *list_n) return;
+  blend_one<true>(idx, d2, tgt[list[i]].id, k, mode, attr, n_attr, rgb_out, nrm_out);
+}
 
 // the same for a list of ROW ids (the rows a slab exchange completed with foreign candidates)
 __global__ __launch_bounds__(WG) void blend_rows_kernel(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ rows_n, const uint32_t* __restrict__ idx,
@@ -245,6 +268,13 @@ __global__ __launch_bounds__(WG) void blend_rows_kernel(const uint32_t* __restri
   const uint32_t i = blockIdx.x * WG + threadIdx.x;
   if (i >= *rows_n) return;
   blend_one(idx, d2, rows[i], k, mode, attr, n_attr, rgb_out, nrm_out);
+}
+__global__ __launch_bounds__(WG) void blend_rows_keep_kernel(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ rows_n, const uint32_t* __restrict__ idx,
+                                                             const double* __restrict__ d2, int k, int mode, const Attr* __restrict__ attr, uint32_t n_attr,
+                                                             float* __restrict__ rgb_out, float* __restrict__ nrm_out) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= *rows_n) return;
+  blend_one<true>(idx, d2, rows[i], k, mode, attr, n_attr, rgb_out, nrm_out);
 }
 
 // cyclic Jacobi on a symmetric 3x3 (fp64), same sweep order as the oracle
@@ -412,14 +442,16 @@ void pt_launch_pack_attr(const uint8_t* rgb, const float* nrm, uint32_t n, Attr*
   hipLaunchKernelGGL(pack_attr_kernel, grid_for(n), dim3(WG), 0, s, rgb, nrm, n, attr);
 }
 void pt_launch_blend_rows(const uint32_t* rows, const uint32_t* rows_n, uint32_t m_max, const uint32_t* idx, const double* d2, int k, int mode,
-                          const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s) {
+                          const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty) {
   if (!m_max) return;
-  hipLaunchKernelGGL(blend_rows_kernel, grid_for(m_max), dim3(WG), 0, s, rows, rows_n, idx, d2, k, mode, attr, n_attr, rgb_out, nrm_out);
+  if (keep_empty) hipLaunchKernelGGL(blend_rows_keep_kernel, grid_for(m_max), dim3(WG), 0, s, rows, rows_n, idx, d2, k, mode, attr, n_attr, rgb_out, nrm_out);
+  else hipLaunchKernelGGL(blend_rows_kernel, grid_for(m_max), dim3(WG), 0, s, rows, rows_n, idx, d2, k, mode, attr, n_attr, rgb_out, nrm_out);
 }
 void pt_launch_blend(const uint32_t* idx, const double* d2, uint32_t m, int k, int mode, const Attr* attr, uint32_t n_attr, float* rgb_out,
-                     float* nrm_out, hipStream_t s) {
+                     float* nrm_out, hipStream_t s, bool keep_empty) {
   if (!m) return;
-  hipLaunchKernelGGL(blend_kernel, grid_for(m), dim3(WG), 0, s, idx, d2, m, k, mode, attr, n_attr, rgb_out, nrm_out);
+  if (keep_empty) hipLaunchKernelGGL(blend_keep_kernel, grid_for(m), dim3(WG), 0, s, idx, d2, m, k, mode, attr, n_attr, rgb_out, nrm_out);
+  else hipLaunchKernelGGL(blend_kernel, grid_for(m), dim3(WG), 0, s, idx, d2, m, k, mode, attr, n_attr, rgb_out, nrm_out);
 }
 void pt_launch_blend_weighted(const uint32_t* idx, const double* w, uint32_t m, int k, const Attr* attr, uint32_t n_attr, float* rgb_out,
                               float* nrm_out, hipStream_t s) {
@@ -428,14 +460,15 @@ void pt_launch_blend_weighted(const uint32_t* idx, const double* w, uint32_t m, 
 }
 template <class Rec>
 void pt_launch_blend_list(const uint32_t* list, const uint32_t* list_n, uint32_t m_max, const Rec* tgt, const uint32_t* idx, const double* d2, int k,
-                          int mode, const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s) {
+                          int mode, const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty) {
   if (!m_max) return;
-  hipLaunchKernelGGL(blend_list_kernel<Rec>, grid_for(m_max), dim3(WG), 0, s, list, list_n, tgt, idx, d2, k, mode, attr, n_attr, rgb_out, nrm_out);
+  if (keep_empty) hipLaunchKernelGGL(blend_list_keep_kernel<Rec>, grid_for(m_max), dim3(WG), 0, s, list, list_n, tgt, idx, d2, k, mode, attr, n_attr, rgb_out, nrm_out);
+  else hipLaunchKernelGGL(blend_list_kernel<Rec>, grid_for(m_max), dim3(WG), 0, s, list, list_n, tgt, idx, d2, k, mode, attr, n_attr, rgb_out, nrm_out);
 }
 template void pt_launch_blend_list<RecF>(const uint32_t*, const uint32_t*, uint32_t, const RecF*, const uint32_t*, const double*, int, int, const Attr*,
-                                         uint32_t, float*, float*, hipStream_t);
+                                         uint32_t, float*, float*, hipStream_t, bool);
 template void pt_launch_blend_list<RecD>(const uint32_t*, const uint32_t*, uint32_t, const RecD*, const uint32_t*, const double*, int, int, const Attr*,
-                                         uint32_t, float*, float*, hipStream_t);
+                                         uint32_t, float*, float*, hipStream_t, bool);
 template <class T>
 void pt_launch_pca(const uint32_t* idx, uint32_t m, int k, const T* x, const T* y, const T* z, uint32_t n, const Attr* attr, float* nrm_out,
                    hipStream_t s) {

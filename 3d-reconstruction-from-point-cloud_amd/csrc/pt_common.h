@@ -130,4 +130,8 @@ __device__ inline uint32_t block_excl_scan_n(uint32_t v, uint32_t* wsum, uint32_
 }
 __device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) { return block_excl_scan_n<4>(v, wsum, total); }
 
+// how far a target still reaches for other slabs: its k-th squared distance, but no farther than the max_dist cap (cap2 = +inf: off).
+// (a NaN k-th distance stays NaN: the slab tests then say "not needed", as they always did)
+__device__ inline double pt_reach2(double kth, double cap2) { return cap2 < kth ? cap2 : kth; }
+
 #endif

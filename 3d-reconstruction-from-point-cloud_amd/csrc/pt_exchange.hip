@@ -22,7 +22,7 @@ __device__ inline bool slab_needed(double c, double kth, double lo, double hi) {
 
 template <class T, bool FILL>
 __global__ __launch_bounds__(XW) void xreq_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z, const double* __restrict__ d2,
-                                                  uint32_t m, int k, int axis, const double* __restrict__ bounds, int g, int me,
+                                                  uint32_t m, int k, int axis, const double* __restrict__ bounds, int g, int me, double cap2,
                                                   uint32_t* __restrict__ counts, const uint32_t* __restrict__ off, uint32_t* __restrict__ cursor,
                                                   double* __restrict__ req, uint32_t* __restrict__ req_row) {
   // One GLOBAL atomic per workgroup and destination, not per target (round 4; measured on config 4 as eight logical slabs: the 70 k crossing
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(XW) void xreq_kernel(const T* __restrict__ x, const
   const uint32_t per = ((m + gridDim.x - 1) / gridDim.x + XW - 1) / XW * XW, t0 = blockIdx.x * per, t1 = min(m, t0 + per);
   for (uint32_t t = t0 + threadIdx.x; t < t1; t += XW) {
     const double c = (double)(axis == 0 ? x[t] : (axis == 1 ? y[t] : z[t]));
-    const double kth = d2[(size_t)t * k + (k - 1)];
+    const double kth = pt_reach2(d2[(size_t)t * k + (k - 1)], cap2);
     for (int s = 0; s < g; ++s)
       if (s != me && slab_needed(c, kth, bounds[s], bounds[s + 1])) atomicAdd(&cnt[s], 1u);
   }
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(XW) void xreq_kernel(const T* __restrict__ x, const
     __syncthreads();
     for (uint32_t t = t0 + threadIdx.x; t < t1; t += XW) {
       const double c = (double)(axis == 0 ? x[t] : (axis == 1 ? y[t] : z[t]));
-      const double kth = d2[(size_t)t * k + (k - 1)];
+      const double kth = pt_reach2(d2[(size_t)t * k + (k - 1)], cap2);
       for (int s = 0; s < g; ++s) {
         if (s != me && slab_needed(c, kth, bounds[s], bounds[s + 1])) {
           const uint32_t pos = off[s] + base[s] + atomicAdd(&cnt[s], 1u);
@@ -152,13 +152,12 @@ __global__ __launch_bounds__(XW) void xmerge_attr_kernel(const uint32_t* __restr
   flags[r] = 1;
 }
 // the blend of pt_attr.hip's blend_one for the listed rows, from the records the merge carried along
-__global__ __launch_bounds__(XW) void blend_rows_attr_kernel(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ rows_n, const uint32_t* __restrict__ idx,
-                                                             const double* __restrict__ d2, const Attr* __restrict__ rattr, int k, int mode, float* __restrict__ rgb_out,
-                                                             float* __restrict__ nrm_out) {
-  const uint32_t i = blockIdx.x * XW + threadIdx.x;
-  if (i >= *rows_n) return;
-  const uint32_t t = rows[i];
+// (KEEP: a row without any entry is not written -- the blends of a context with a max_dist cap)
+template <bool KEEP>
+__device__ inline void blend_row_attr(const uint32_t* __restrict__ idx, const double* __restrict__ d2, const Attr* __restrict__ rattr, uint32_t t, int k, int mode,
+                                      float* __restrict__ rgb_out, float* __restrict__ nrm_out) {
   double wsum = 0.0, c[3] = {0, 0, 0}, nn[3] = {0, 0, 0};
+  bool any = false;
   for (int j = 0; j < k; ++j) {
     if (idx[(size_t)t * k + j] == PT_NOIDX_U) continue;
     const Attr a = rattr[(size_t)t * k + j];
@@ -166,7 +165,9 @@ __global__ __launch_bounds__(XW) void blend_rows_attr_kernel(const uint32_t* __r
     wsum += w;
     c[0] += w * (double)(a.rgba & 0xFFu); c[1] += w * (double)((a.rgba >> 8) & 0xFFu); c[2] += w * (double)((a.rgba >> 16) & 0xFFu);
     nn[0] += w * (double)a.nx; nn[1] += w * (double)a.ny; nn[2] += w * (double)a.nz;
+    any = true;
   }
+  if (KEEP && !any) return;
   if (wsum > 0.0) {
     const double iw = 1.0 / wsum;
     for (int q = 0; q < 3; ++q) { c[q] *= iw; nn[q] *= iw; }
@@ -175,6 +176,20 @@ __global__ __launch_bounds__(XW) void blend_rows_attr_kernel(const uint32_t* __r
   }
   if (rgb_out) { rgb_out[3 * (size_t)t] = (float)c[0]; rgb_out[3 * (size_t)t + 1] = (float)c[1]; rgb_out[3 * (size_t)t + 2] = (float)c[2]; }
   if (nrm_out) { nrm_out[3 * (size_t)t] = (float)nn[0]; nrm_out[3 * (size_t)t + 1] = (float)nn[1]; nrm_out[3 * (size_t)t + 2] = (float)nn[2]; }
+}
+__global__ __launch_bounds__(XW) void blend_rows_attr_kernel(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ rows_n, const uint32_t* __restrict__ idx,
+                                                             const double* __restrict__ d2, const Attr* __restrict__ rattr, int k, int mode, float* __restrict__ rgb_out,
+                                                             float* __restrict__ nrm_out) {
+  const uint32_t i = blockIdx.x * XW + threadIdx.x;
+  if (i >= *rows_n) return;
+  blend_row_attr<false>(idx, d2, rattr, rows[i], k, mode, rgb_out, nrm_out);
+}
+__global__ __launch_bounds__(XW) void blend_rows_attr_keep_kernel(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ rows_n, const uint32_t* __restrict__ idx,
+                                                                  const double* __restrict__ d2, const Attr* __restrict__ rattr, int k, int mode, float* __restrict__ rgb_out,
+                                                                  float* __restrict__ nrm_out) {
+  const uint32_t i = blockIdx.x * XW + threadIdx.x;
+  if (i >= *rows_n) return;
+  blend_row_attr<true>(idx, d2, rattr, rows[i], k, mode, rgb_out, nrm_out);
 }
 // is gidx strictly ascending?  *flag |= 1 when it is not
 __global__ __launch_bounds__(XW) void ascending_kernel(const uint32_t* __restrict__ gidx, uint32_t n, uint32_t* flag) {
@@ -202,15 +217,15 @@ static inline dim3 xgrid(uint32_t n) { return dim3((n + XW - 1) / XW); }
 
 template <class T>
 void pt_launch_xreq(bool fill, const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g, int me,
-                    uint32_t* counts, const uint32_t* off, uint32_t* cursor, double* req, uint32_t* req_row, hipStream_t s) {
+                    double cap2, uint32_t* counts, const uint32_t* off, uint32_t* cursor, double* req, uint32_t* req_row, hipStream_t s) {
   if (!m) return;
   const dim3 grid(std::min<uint32_t>((m + XW - 1) / XW, 2048u));       // a piece of the targets per workgroup (xreq_kernel)
-  if (fill) hipLaunchKernelGGL((xreq_kernel<T, true>), grid, dim3(XW), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, me, counts, off, cursor, req, req_row);
-  else hipLaunchKernelGGL((xreq_kernel<T, false>), grid, dim3(XW), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, me, counts, off, cursor, req, req_row);
+  if (fill) hipLaunchKernelGGL((xreq_kernel<T, true>), grid, dim3(XW), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, me, cap2, counts, off, cursor, req, req_row);
+  else hipLaunchKernelGGL((xreq_kernel<T, false>), grid, dim3(XW), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, me, cap2, counts, off, cursor, req, req_row);
 }
-template void pt_launch_xreq<float>(bool, const float*, const float*, const float*, const double*, uint32_t, int, int, const double*, int, int, uint32_t*,
+template void pt_launch_xreq<float>(bool, const float*, const float*, const float*, const double*, uint32_t, int, int, const double*, int, int, double, uint32_t*,
                                     const uint32_t*, uint32_t*, double*, uint32_t*, hipStream_t);
-template void pt_launch_xreq<double>(bool, const double*, const double*, const double*, const double*, uint32_t, int, int, const double*, int, int, uint32_t*,
+template void pt_launch_xreq<double>(bool, const double*, const double*, const double*, const double*, uint32_t, int, int, const double*, int, int, double, uint32_t*,
                                      const uint32_t*, uint32_t*, double*, uint32_t*, hipStream_t);
 template <class T>
 void pt_launch_xunpack(const double* rreq, uint32_t r, T* xyz, double* bound, hipStream_t s) {
@@ -243,8 +258,10 @@ void pt_launch_xmerge_attr(const uint32_t* rows, uint32_t cnt, const uint32_t* b
   if (cnt) hipLaunchKernelGGL(xmerge_attr_kernel, xgrid(cnt), dim3(XW), 0, s, rows, cnt, bi, bd, ba, k, idx, d2, rattr, flags, gidx, n, attr);
 }
 void pt_launch_blend_rows_attr(const uint32_t* rows, const uint32_t* rows_n, uint32_t m_max, const uint32_t* idx, const double* d2, const Attr* rattr, int k, int mode,
-                               float* rgb_out, float* nrm_out, hipStream_t s) {
-  if (m_max) hipLaunchKernelGGL(blend_rows_attr_kernel, xgrid(m_max), dim3(XW), 0, s, rows, rows_n, idx, d2, rattr, k, mode, rgb_out, nrm_out);
+                               float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty) {
+  if (!m_max) return;
+  if (keep_empty) hipLaunchKernelGGL(blend_rows_attr_keep_kernel, xgrid(m_max), dim3(XW), 0, s, rows, rows_n, idx, d2, rattr, k, mode, rgb_out, nrm_out);
+  else hipLaunchKernelGGL(blend_rows_attr_kernel, xgrid(m_max), dim3(XW), 0, s, rows, rows_n, idx, d2, rattr, k, mode, rgb_out, nrm_out);
 }
 void pt_launch_ascending(const uint32_t* gidx, uint32_t n, uint32_t* flag, hipStream_t s) {
   if (n > 1) hipLaunchKernelGGL(ascending_kernel, xgrid(n), dim3(XW), 0, s, gidx, n, flag);

@@ -108,21 +108,24 @@ constexpr int PT_TILE_MAX_K = 32;      // beyond this the group kernel answers e
 void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start,
                         int k, uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr,
                         int mode, float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry,
-                        uint32_t* retry_n, const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound = nullptr);
+                        uint32_t* retry_n, const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound = nullptr,
+                        double cap2 = INFINITY);   // bound (per target) and / or cap2 < +inf (max_dist squared): the bounded variants; with attr they blend too
 template <class T>
 void pt_launch_request_pack(const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g,
-                            int my_slab, uint32_t* count, uint32_t* sel, double* pkt, hipStream_t s);
+                            int my_slab, double cap2, uint32_t* count, uint32_t* sel, double* pkt, hipStream_t s);
 void pt_launch_merge(const uint32_t* idx_lists, const double* d2_lists, int g, uint32_t m, int k, uint32_t* idx_out,
                      double* d2_out, hipStream_t s);
 // streamed sources: merge the running best lists (u64 ids) with one chunk's lists (chunk-local u32 ids + base), out of place
 template <class T>
 void pt_launch_stream_sweep(const T* xyz_planar, const unsigned long long* best_idx, const double* best_d2, uint32_t m, int k, uint32_t chunk, int backward,
-                            uint32_t* first, const double lo[3], const double hi[3], double margin, double* bound, uint32_t* count, hipStream_t s);
+                            uint32_t* first, const double lo[3], const double hi[3], double margin, double cap2, double* bound, uint32_t* count, hipStream_t s);
 void pt_launch_merge_stream(const unsigned long long* best_idx, const double* best_d2, const uint32_t* chunk_idx, const double* chunk_d2,
                             unsigned long long base, uint32_t m, int k, unsigned long long* out_idx, double* out_d2, hipStream_t s);
 template <class T>
 void pt_launch_slab_need(const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis,
-                         const double* bounds_dev, int g, int my_slab, uint8_t* need, hipStream_t s);
+                         const double* bounds_dev, int g, int my_slab, double cap2, uint8_t* need, hipStream_t s);
+// per-target bounds of a capped query: out[t] = min(bound2[t], cap2) (bound2 may be null: cap2)
+void pt_launch_cap_bounds(const double* bound2, uint32_t m, double cap2, double* out, hipStream_t s);
 
 // ---- pt_attr.hip ------------------------------------------------------------------------------
 // SURVEY.md Appendix C generator.  Writes planar xyz (T) for indices [0,n_total) whose `axis` coordinate is
@@ -141,9 +144,10 @@ void pt_launch_blend_weighted(const uint32_t* idx, const double* w, uint32_t m, 
                               float* nrm_out, hipStream_t s);
 template <class Rec>
 void pt_launch_blend_list(const uint32_t* list, const uint32_t* list_n, uint32_t m_max, const Rec* tgt, const uint32_t* idx, const double* d2, int k,
-                          int mode, const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s);
+                          int mode, const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty = false);
+// keep_empty (a context with a max_dist cap): rows without any neighbour are not written
 void pt_launch_blend(const uint32_t* idx, const double* d2, uint32_t m, int k, int mode, const Attr* attr, uint32_t n_attr,
-                     float* rgb_out, float* nrm_out, hipStream_t s);
+                     float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty = false);
 template <class T>
 void pt_launch_pca(const uint32_t* idx, uint32_t m, int k, const T* x, const T* y, const T* z, uint32_t n, const Attr* attr,
                    float* nrm_out, hipStream_t s);
@@ -169,7 +173,7 @@ void pt_launch_dilate_pad(const uint32_t* tex, uint32_t* tmp, uint32_t* out, int
 // fill = true writes packets {x, y, z, k-th d2} at off[s] + cursor[s]++ (cursor zeroed by the caller) and the row they came from
 template <class T>
 void pt_launch_xreq(bool fill, const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g, int me,
-                    uint32_t* counts, const uint32_t* off, uint32_t* cursor, double* req, uint32_t* req_row, hipStream_t s);
+                    double cap2, uint32_t* counts, const uint32_t* off, uint32_t* cursor, double* req, uint32_t* req_row, hipStream_t s);
 template <class T>
 void pt_launch_xunpack(const double* rreq, uint32_t r, T* xyz_planar, double* bound, hipStream_t s);
 // merge bucket answers (bi, bd)[cnt][k] into rows[e]'s lists in place; flags[row] = 1 for every row touched
@@ -182,11 +186,11 @@ void pt_launch_xgather_attr(const uint32_t* ids, size_t count, const uint32_t* g
 void pt_launch_xmerge_attr(const uint32_t* rows, uint32_t cnt, const uint32_t* bi, const double* bd, const Attr* ba, int k, uint32_t* idx, double* d2, Attr* rattr,
                            uint8_t* flags, const uint32_t* gidx, uint32_t n, const Attr* attr, hipStream_t s);
 void pt_launch_blend_rows_attr(const uint32_t* rows, const uint32_t* rows_n, uint32_t m_max, const uint32_t* idx, const double* d2, const Attr* rattr, int k, int mode,
-                               float* rgb_out, float* nrm_out, hipStream_t s);
+                               float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty = false);
 void pt_launch_ascending(const uint32_t* gidx, uint32_t n, uint32_t* flag, hipStream_t s);                             // *flag |= 1 unless gidx is strictly ascending
 // blend of the listed rows (row ids, not sorted positions) from their idx / d2 lists
 void pt_launch_blend_rows(const uint32_t* rows, const uint32_t* rows_n, uint32_t m_max, const uint32_t* idx, const double* d2, int k, int mode,
-                          const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s);
+                          const Attr* attr, uint32_t n_attr, float* rgb_out, float* nrm_out, hipStream_t s, bool keep_empty = false);
 
 // ---- pt_refine.hip ------------------------------------------------------------------------------
 // cells with more than `threshold` points become nodes (cell_node[c] = node id + 1, else 0; *node_count counts them, also past node_cap)

@@ -1317,11 +1317,14 @@ __device__ inline void glds16(const uint4* g, uint4* lbase) {
 struct TileBlend { const Attr* attr; uint32_t n_attr; int mode; float* rgb_out; float* nrm_out; };
 // Second chance for blocks whose region is over this geometry's LDS budget but within the large geometry's: their ids go
 // to `retry` (retry != null), and a second launch (blocks != null: blockIdx.x indexes that list) takes them.
-struct TileBlocks { const uint32_t* blocks; uint32_t* retry; uint32_t* retry_n; uint32_t retry_cap; const double* bound; };
-// BND (fp32 clouds, no fused blend): every target brings a radius bound[id] -- the k-th squared distance it already has from another
-// part of the cloud (the chunks of a streamed source, pt_stream_query) -- and only points with d2 <= bound matter.  The bound joins
-// pass 1's own (whichever is smaller prunes pass 2), settles targets whose k-th neighbour lies beyond ring 1 when the bound does not,
-// and lets targets with fewer than k points in reach finish with a short list (the rest NOIDX / +inf, as a bounded query returns).
+struct TileBlocks { const uint32_t* blocks; uint32_t* retry; uint32_t* retry_n; uint32_t retry_cap; const double* bound; double cap2; };
+// BND: every target brings a radius bound, min(bound[id], cap2) -- bound[id] (may be null) the k-th squared distance it already has from
+// another part of the cloud (the chunks of a streamed source, pt_stream_query), cap2 the context's uniform "max_dist" squared (+inf when
+// off) -- and only points with d2 <= bound matter.  The bound joins pass 1's own (whichever is smaller prunes pass 2), settles targets
+// whose k-th neighbour lies beyond ring 1 when the bound does not, drops queued candidates whose EXACT d2 is beyond it, and lets targets
+// with fewer than k points in reach finish with a short list (the rest NOIDX / +inf, as a bounded query returns).  With BLEND too (the
+// capped fused query) a row with at least one neighbour is blended over what it has, and a row with none is not written; those
+// variants read cap2 only (no caller brings per-target bounds to a blended query), which keeps the bound in a scalar register.
 // fp64 clouds (DBL): the LDS image and the two fp32 passes work on fp32-ROUNDED coordinates (the build's shadow records,
 // whose id field is the sorted position), under a bound widened by the rounding; pass 3 fetches the exact 32-byte
 // records of the queued candidates by position.  src / tgt: the exact records; e_src: largest |coordinate| rounding
@@ -1552,9 +1555,9 @@ __global__ __launch_bounds__(TWG, TILE_CAP > 5000 ? 1 : (TWG == 384 ? 3 : 4)) vo
     //      still be valid but loosen the bound: measured 3.7 % of the targets overflow the queue with 3K/4, 17 % with K/2. ----
     const int sx = (u[0] - (double)cc[0]) >= 0.5 ? 0 : -1, sy = (u[1] - (double)cc[1]) >= 0.5 ? 0 : -1, sz = (u[2] - (double)cc[2]) >= 0.5 ? 0 : -1;
     double bnd = INFINITY;
-    if constexpr (BND) {
-      static_assert(!BLEND, "the bounded variant is built without the fused blend");
-      if (active) bnd = tb.bound[tr.id];
+    if constexpr (BND && BLEND) bnd = tb.cap2;          // (the fused blend comes with the uniform cap only: a scalar, no registers per lane)
+    else if constexpr (BND) {
+      if (active) bnd = tb.bound ? fmin(tb.bound[tr.id], tb.cap2) : tb.cap2;
     }
     const bool scan1 = active && !(BND && bnd < 0.0);      // (a negative bound -- "nothing from this cloud" -- skips pass 1 too; pass 2 prunes itself)
     float l32[K];
@@ -1690,7 +1693,17 @@ __global__ __launch_bounds__(TWG, TILE_CAP > 5000 ? 1 : (TWG == 384 ? 3 : 4)) vo
         const RecF r = lrec[queue[((threadIdx.x & ~3u) + seg) * (TILE_LCAP + 1) + off]];
         if constexpr (DBL) { const RecD rd = dd.src[r.id]; od[j] = dist2(q, rd); oi[j] = rd.id; }     // r.id: sorted position of the exact record
         else { od[j] = dist2(q, r); oi[j] = r.id; }
+        if constexpr (BND) if (od[j] > bnd) { od[j] = INFINITY; oi[j] = PT_NOIDX_U; }   // let through by the widened fp32 bound only
       }
+    }
+    // (BND) entries that survived the exact test -- the list is short when fewer than k did; without BND every queued entry counts
+    uint32_t nval = nq;
+    if constexpr (BND) {
+      nval = 0;
+#pragma unroll
+      for (int j = 0; j < TILE_QCAP / 4; ++j) nval += oi[j] != PT_NOIDX_U ? 1u : 0u;
+      nval += dpp_u32<DPP_QP_1032>(nval);
+      nval += dpp_u32<DPP_QP_2301>(nval);
     }
     // Ranking counts, for each of my entries, the queue entries with a smaller distance.  Equal distances (rare) leave
     // two entries with the same count: the ranks then do not add up to 0 + 1 + ... + (nq-1) and the quad redoes the count
@@ -1721,7 +1734,7 @@ __global__ __launch_bounds__(TWG, TILE_CAP > 5000 ? 1 : (TWG == 384 ? 3 : 4)) vo
       for (int j = 0; j < TILE_QCAP / 4; ++j) rs += (oi[j] != PT_NOIDX_U) ? rk[j] : 0;
       rs += (int)dpp_u32<DPP_QP_1032>((uint32_t)rs);
       rs += (int)dpp_u32<DPP_QP_2301>((uint32_t)rs);
-      const uint32_t nv = overflow ? 0u : nq;
+      const uint32_t nv = overflow ? 0u : nval;
       if ((uint32_t)rs != nv * (nv - 1u) / 2u) {       // quad-uniform
 #pragma unroll
         for (int j = 0; j < TILE_QCAP / 4; ++j) rk[j] = 0;
@@ -1759,7 +1772,7 @@ __global__ __launch_bounds__(TWG, TILE_CAP > 5000 ? 1 : (TWG == 384 ? 3 : 4)) vo
 #pragma unroll
           for (int j = 0; j < NE; ++j)
             if (oi[j] != PT_NOIDX_U && rk[j] < k) { out_idx[row + rk[j]] = oi[j]; if (out_d2) out_d2[row + rk[j]] = od[j]; }
-          for (uint32_t sl = nq + ql; sl < (uint32_t)k; sl += 4) { out_idx[row + sl] = PT_NOIDX_U; if (out_d2) out_d2[row + sl] = INFINITY; }
+          for (uint32_t sl = nval + ql; sl < (uint32_t)k; sl += 4) { out_idx[row + sl] = PT_NOIDX_U; if (out_d2) out_d2[row + sl] = INFINITY; }
         };
         if constexpr (!BLEND) store_results();
         if constexpr (BLEND) {
@@ -1802,7 +1815,7 @@ __global__ __launch_bounds__(TWG, TILE_CAP > 5000 ? 1 : (TWG == 384 ? 3 : 4)) vo
             n0 *= sc; n1 *= sc; n2 *= sc;
           }
           float* o = (ql == 0) ? bl.rgb_out : bl.nrm_out;
-          if (ql < 2 && o) {
+          if (ql < 2 && o && (!BND || nval != 0)) {            // (capped: a row with no neighbour in reach keeps what the caller put there)
             o[3 * (size_t)tr.id] = (float)(ql == 0 ? c0 : n0); o[3 * (size_t)tr.id + 1] = (float)(ql == 0 ? c1 : n1);
             o[3 * (size_t)tr.id + 2] = (float)(ql == 0 ? c2 : n2);
           }
@@ -1868,11 +1881,11 @@ __global__ __launch_bounds__(WG) void merge_stream_kernel(const unsigned long lo
 template <class T>
 __global__ __launch_bounds__(WG) void slab_need_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z,
                                                        const double* __restrict__ d2, uint32_t m, int k, int axis,
-                                                       const double* __restrict__ bounds, int g, int my_slab, uint8_t* __restrict__ need) {
+                                                       const double* __restrict__ bounds, int g, int my_slab, double cap2, uint8_t* __restrict__ need) {
   const uint32_t t = blockIdx.x * WG + threadIdx.x;
   if (t >= m) return;
   const double c = (double)(axis == 0 ? x[t] : (axis == 1 ? y[t] : z[t]));
-  const double kth = d2[(size_t)t * k + (k - 1)];
+  const double kth = pt_reach2(d2[(size_t)t * k + (k - 1)], cap2);
   for (int s = 0; s < g; ++s) {
     uint8_t v = 0;
     if (s != my_slab) {
@@ -1890,12 +1903,12 @@ __global__ __launch_bounds__(WG) void slab_need_kernel(const T* __restrict__ x, 
 template <class T>
 __global__ __launch_bounds__(WG) void request_pack_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z,
                                                           const double* __restrict__ d2, uint32_t m, int k, int axis,
-                                                          const double* __restrict__ bounds, int g, int my_slab, uint32_t* __restrict__ count,
+                                                          const double* __restrict__ bounds, int g, int my_slab, double cap2, uint32_t* __restrict__ count,
                                                           uint32_t* __restrict__ sel, double* __restrict__ pkt) {
   const uint32_t t = blockIdx.x * WG + threadIdx.x;
   if (t >= m) return;
   const double c = (double)(axis == 0 ? x[t] : (axis == 1 ? y[t] : z[t]));
-  const double kth = d2[(size_t)t * k + (k - 1)];
+  const double kth = pt_reach2(d2[(size_t)t * k + (k - 1)], cap2);
   uint64_t mask = 0;
   for (int s = 0; s < g; ++s) {
     if (s == my_slab) continue;
@@ -1914,14 +1927,14 @@ __global__ __launch_bounds__(WG) void request_pack_kernel(const T* __restrict__ 
 
 template <class T>
 void pt_launch_request_pack(const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g,
-                            int my_slab, uint32_t* count, uint32_t* sel, double* pkt, hipStream_t s) {
+                            int my_slab, double cap2, uint32_t* count, uint32_t* sel, double* pkt, hipStream_t s) {
   if (!m) return;
-  hipLaunchKernelGGL(request_pack_kernel<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, my_slab, count, sel, pkt);
+  hipLaunchKernelGGL(request_pack_kernel<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, my_slab, cap2, count, sel, pkt);
 }
-template void pt_launch_request_pack<float>(const float*, const float*, const float*, const double*, uint32_t, int, int, const double*, int, int,
+template void pt_launch_request_pack<float>(const float*, const float*, const float*, const double*, uint32_t, int, int, const double*, int, int, double,
                                             uint32_t*, uint32_t*, double*, hipStream_t);
-template void pt_launch_request_pack<double>(const double*, const double*, const double*, const double*, uint32_t, int, int, const double*, int,
-                                             int, uint32_t*, uint32_t*, double*, hipStream_t);
+template void pt_launch_request_pack<double>(const double*, const double*, const double*, const double*, uint32_t, int, int, const double*, int, int,
+                                             double, uint32_t*, uint32_t*, double*, hipStream_t);
 
 template <class Rec>
 void pt_launch_knn(const GridParams& gp, const Rec* src, const uint32_t* cell_start, const Rec* tgt, uint32_t m, int k, const double* bound2,
@@ -2074,31 +2087,40 @@ template void pt_launch_knn_wave<RecD>(const GridParams&, const RecD*, const uin
 void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start, int k,
                         uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr, int mode,
                         float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry, uint32_t* retry_n,
-                        const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound) {
+                        const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound, double cap2) {
   const uint32_t nb = blocks ? nblocks_listed : (uint32_t)gp.nblocks;
   if (!nb) return;
   const TileBlend bl{attr, n_attr, mode, rgb_out, nrm_out};
-  const TileBlocks tbk{blocks, retry, retry_n, (uint32_t)PT_TILE_CAP_LARGE, bound};
-  if (bound) {                                       // bounded variant: no fused blend (pt_api.hip only sends those here); round 4: fp64 clouds and k in 25..32 too
-#define PT_TILE_LAUNCHB1(KK, CAP, TH, WD, DB, KCH)                                                                                                     \
-  hipLaunchKernelGGL((knn_tile_kernel<KK, CAP, TH, WD, false, DB, KCH, true>), dim3(nb), dim3(TH), 0, s, gp, src, cell_start, tgt, tblock_start, k, \
+  const TileBlocks tbk{blocks, retry, retry_n, (uint32_t)PT_TILE_CAP_LARGE, bound, cap2};
+  if (bound || cap2 < INFINITY) {
+    // Bounded variants: per-target bounds (pt_stream_query's chunks; never with attr: the blended variants read cap2 only), the context's
+    // max_dist (cap2), or both.  The
+    // geometries are the unbounded launcher's below, medium one included; `attr` selects the fused blend (capped resident queries).
+#define PT_TILE_LAUNCHB1(KK, CAP, TH, WD, BL, DB, KCH)                                                                                                 \
+  hipLaunchKernelGGL((knn_tile_kernel<KK, CAP, TH, WD, BL, DB, KCH, true>), dim3(nb), dim3(TH), 0, s, gp, src, cell_start, tgt, tblock_start, k, \
                      out_idx, out_d2, todo, todo_n, bl, tbk, TileDouble{src_exact, tgt_exact, e_src})
-#define PT_TILE_LAUNCHB(KK, CAP, TH, KCH)                             \
-  do {                                                                \
-    if (src_exact) PT_TILE_LAUNCHB1(KK, CAP, TH, false, true, KCH);   \
-    else PT_TILE_LAUNCHB1(KK, CAP, TH, false, false, KCH);            \
+#define PT_TILE_LAUNCHB(KK, CAP, TH, WD, KCH)                                 \
+  do {                                                                        \
+    if (src_exact) {                                                          \
+      if (attr) PT_TILE_LAUNCHB1(KK, CAP, TH, WD, true, true, KCH);           \
+      else PT_TILE_LAUNCHB1(KK, CAP, TH, WD, false, true, KCH);               \
+    } else {                                                                  \
+      if (attr) PT_TILE_LAUNCHB1(KK, CAP, TH, WD, true, false, KCH);          \
+      else PT_TILE_LAUNCHB1(KK, CAP, TH, WD, false, false, KCH);              \
+    }                                                                         \
   } while (0)
-    if (k > 24) {
-      if (src_exact) PT_TILE_LAUNCHB1(32, PT_TILE_CAP_WIDE, 512, true, true, 32);
-      else PT_TILE_LAUNCHB1(32, PT_TILE_CAP_WIDE, 512, true, false, 32);
+    if (k > 24) PT_TILE_LAUNCHB(32, PT_TILE_CAP_WIDE, 512, true, 32);
+    else if (geometry == 4 && k > 16 && cap2 < INFINITY) {      // (uncapped streamed chunks keep the large geometry they always had)
+      if (k <= 20) PT_TILE_LAUNCHB(32, PT_TILE_CAP_SMALL_16, 384, false, 20);
+      else PT_TILE_LAUNCHB(32, PT_TILE_CAP_SMALL_16, 384, false, 24);
     } else if (geometry == 1 && k <= 16) {
-      if (k <= 8) PT_TILE_LAUNCHB(8, PT_TILE_CAP_SMALL_8, 512, 8);
-      else PT_TILE_LAUNCHB(16, PT_TILE_CAP_SMALL_16, 512, 16);
+      if (k <= 8) PT_TILE_LAUNCHB(8, PT_TILE_CAP_SMALL_8, 512, false, 8);
+      else PT_TILE_LAUNCHB(16, PT_TILE_CAP_SMALL_16, 512, false, 16);
     } else {
-      if (k <= 8) PT_TILE_LAUNCHB(8, PT_TILE_CAP_LARGE, 768, 8);
-      else if (k <= 16) PT_TILE_LAUNCHB(16, PT_TILE_CAP_LARGE, 768, 16);
-      else if (k <= 20) PT_TILE_LAUNCHB(32, PT_TILE_CAP_LARGE, 768, 20);
-      else PT_TILE_LAUNCHB(32, PT_TILE_CAP_LARGE, 768, 24);
+      if (k <= 8) PT_TILE_LAUNCHB(8, PT_TILE_CAP_LARGE, 768, false, 8);
+      else if (k <= 16) PT_TILE_LAUNCHB(16, PT_TILE_CAP_LARGE, 768, false, 16);
+      else if (k <= 20) PT_TILE_LAUNCHB(32, PT_TILE_CAP_LARGE, 768, false, 20);
+      else PT_TILE_LAUNCHB(32, PT_TILE_CAP_LARGE, 768, false, 24);
     }
 #undef PT_TILE_LAUNCHB
 #undef PT_TILE_LAUNCHB1
@@ -2157,11 +2179,13 @@ void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* c
 //   backward sweep, chunk c:  exactly the deferred pairs, first[t] > c, now with a bound.  Every (target, chunk) pair is searched once,
 //                             under a bound that is an upper bound of the target's final k-th distance, so the merged lists are the
 //                             resident search's.
+// With a max_dist cap (cap2 < +inf) nothing is deferred: a target without a list brings cap2 -- it is searched from now on, within the
+// cap, wherever it lies -- and one with a list brings min(k-th, cap2); the backward sweep then finds no pair left.
 template <class T>
 __global__ __launch_bounds__(WG) void stream_sweep_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z,
                                                           const unsigned long long* __restrict__ bi, const double* __restrict__ bd, uint32_t m, int k,
                                                           uint32_t c, int backward, uint32_t* __restrict__ first, double lx, double ly, double lz, double hx,
-                                                          double hy, double hz, double margin2, double* __restrict__ bound, uint32_t* count) {
+                                                          double hy, double hz, double margin2, double cap2, double* __restrict__ bound, uint32_t* count) {
   const uint32_t t = blockIdx.x * WG + threadIdx.x;
   bool reach = false;
   if (t < m) {
@@ -2170,13 +2194,13 @@ __global__ __launch_bounds__(WG) void stream_sweep_kernel(const T* __restrict__ 
 #pragma unroll
     for (int a = 0; a < 3; ++a) { const double g = q[a] < lo[a] ? lo[a] - q[a] : (q[a] > hi[a] ? q[a] - hi[a] : 0.0); d += g * g; }
     const size_t last = (size_t)t * (size_t)k + (size_t)(k - 1);
-    const double kth = bi[last] != ~0ull ? bd[last] : INFINITY;
+    const double kth = fmin(bi[last] != ~0ull ? bd[last] : INFINITY, cap2);
     const uint32_t f = first[t];
     double b;
     if (d != d) b = -1.0;                                       // a NaN coordinate: no neighbours anywhere, the row stays empty
     else if (backward) b = f > c ? kth : -1.0;
     else if (f < c) b = kth;
-    else if (d <= margin2) { b = INFINITY; first[t] = c; }      // inside the box, or within a few point spacings of it
+    else if (d <= margin2 || cap2 < INFINITY) { b = cap2; first[t] = c; }      // inside the box, or within a few point spacings of it (capped: anywhere)
     else b = -1.0;
     bound[t] = b;
     reach = b >= 0.0 && !(d > b);
@@ -2186,14 +2210,14 @@ __global__ __launch_bounds__(WG) void stream_sweep_kernel(const T* __restrict__ 
 }
 template <class T>
 void pt_launch_stream_sweep(const T* xyz_planar, const unsigned long long* best_idx, const double* best_d2, uint32_t m, int k, uint32_t chunk, int backward,
-                            uint32_t* first, const double lo[3], const double hi[3], double margin, double* bound, uint32_t* count, hipStream_t s) {
+                            uint32_t* first, const double lo[3], const double hi[3], double margin, double cap2, double* bound, uint32_t* count, hipStream_t s) {
   if (m) hipLaunchKernelGGL(stream_sweep_kernel<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, xyz_planar, xyz_planar + m, xyz_planar + 2 * (size_t)m, best_idx, best_d2,
-                            m, k, chunk, backward, first, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], margin * margin, bound, count);
+                            m, k, chunk, backward, first, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], margin * margin, cap2, bound, count);
 }
 template void pt_launch_stream_sweep<float>(const float*, const unsigned long long*, const double*, uint32_t, int, uint32_t, int, uint32_t*, const double*, const double*,
-                                            double, double*, uint32_t*, hipStream_t);
+                                            double, double, double*, uint32_t*, hipStream_t);
 template void pt_launch_stream_sweep<double>(const double*, const unsigned long long*, const double*, uint32_t, int, uint32_t, int, uint32_t*, const double*, const double*,
-                                             double, double*, uint32_t*, hipStream_t);
+                                             double, double, double*, uint32_t*, hipStream_t);
 void pt_launch_merge_stream(const unsigned long long* best_idx, const double* best_d2, const uint32_t* chunk_idx, const double* chunk_d2,
                            unsigned long long base, uint32_t m, int k, unsigned long long* out_idx, double* out_d2, hipStream_t s) {
   if (!m) return;
@@ -2209,11 +2233,20 @@ void pt_launch_merge(const uint32_t* idx_lists, const double* d2_lists, int g, u
 
 template <class T>
 void pt_launch_slab_need(const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g,
-                         int my_slab, uint8_t* need, hipStream_t s) {
+                         int my_slab, double cap2, uint8_t* need, hipStream_t s) {
   if (!m) return;
-  hipLaunchKernelGGL(slab_need_kernel<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, my_slab, need);
+  hipLaunchKernelGGL(slab_need_kernel<T>, dim3((m + WG - 1) / WG), dim3(WG), 0, s, x, y, z, d2, m, k, axis, bounds_dev, g, my_slab, cap2, need);
 }
 template void pt_launch_slab_need<float>(const float*, const float*, const float*, const double*, uint32_t, int, int, const double*, int, int,
-                                         uint8_t*, hipStream_t);
+                                         double, uint8_t*, hipStream_t);
 template void pt_launch_slab_need<double>(const double*, const double*, const double*, const double*, uint32_t, int, int, const double*, int,
-                                          int, uint8_t*, hipStream_t);
+                                          int, double, uint8_t*, hipStream_t);
+
+// the per-target bounds of a capped query (the group, hier and wave kernels read theirs by target id): min(bound2[t], cap2), or cap2
+__global__ __launch_bounds__(WG) static void cap_bounds_kernel(const double* __restrict__ bound2, uint32_t m, double cap2, double* __restrict__ out) {
+  const uint32_t t = blockIdx.x * WG + threadIdx.x;
+  if (t < m) out[t] = bound2 ? fmin(bound2[t], cap2) : cap2;
+}
+void pt_launch_cap_bounds(const double* bound2, uint32_t m, double cap2, double* out, hipStream_t s) {
+  if (m) hipLaunchKernelGGL(cap_bounds_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, s, bound2, m, cap2, out);
+}

@@ -20,8 +20,12 @@
 //   --ply-threads T  parser threads for the two input files (default 0 = one per hardware thread; host/ply_fast.h)
 //   --json FILE      phase times (the stdout lines' seconds) and the library's device times / grid statistics as one JSON object
 //   --gpus N         the cloud cut into N spatial slabs, one process per GPU, slab exchange over RCCL (host/sharded.h)
+//   --max-dist R     neighbours farther than R (cloud units, R >= 0) are ignored: a vertex with no cloud point within R keeps its own
+//                    mesh colour and normal in transfer.ply, and the texture is baked from the capped lists (pt_api.h "max_dist");
+//                    stderr reports how many vertices had none, --json adds max_dist and vertices_without_neighbours
 // There is no CPU path: without a usable GPU the tool reports the error and exits non-zero.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -108,6 +112,8 @@ int main(int argc, char** argv) {
   std::string out_name = "transfer.ply", nbr_name, tex_name = "texture.png";                      // texture.png: reference :615
   std::string json_name;                           // --json FILE: the phase times of the stdout lines + pt_stats as one JSON object
   int gpus = 0, rank = -1;
+  double max_dist = INFINITY;                      // --max-dist R (+inf: off)
+  bool max_dist_ok = true;
   bool finalize = false;
   std::string rendezvous;
   // --synthetic N M SEED [--clustered] [--xyz f32|f16|f64]: SURVEY.md Appendix C's generator instead of the two files (the positional
@@ -138,17 +144,32 @@ int main(int argc, char** argv) {
     else if (a == "--clustered") syn_dist = PT_DIST_CLUSTERED;
     else if (a == "--xyz") { const std::string t = val(); syn_type = t == "f16" ? PT_F16 : (t == "f64" ? PT_F64 : PT_F32); }
     else if (a == "--rendezvous-root") { rendezvous = val(); continue; }      // (the launcher's: where its rendezvous directory is made)
+    else if (a == "--max-dist") {
+      const char* v = val();
+      char* end = nullptr;
+      max_dist = std::strtod(v, &end);
+      max_dist_ok = *v && end && !*end && max_dist >= 0.0;       // (NaN fails the comparison)
+    }
     else { std::cerr << "unknown option " << a << std::endl; return 2; }
     for (int j = i_before; j <= i; ++j) passthrough.push_back(argv[j]);
   }
   if (K < 1 || K > PT_MAX_K) { std::cerr << "--k must be in [1, " << PT_MAX_K << "]" << std::endl; return 2; }
   if (resolution < 1 || resolution > 32768 || pad < 0 || pad > 255 || (pad > 0 && !(pad & 1))) { std::cerr << "--resolution must be in [1, 32768], --pad 0 or odd" << std::endl; return 2; }
+  if (!max_dist_ok) { std::cerr << "--max-dist must be a number >= 0" << std::endl; return 2; }
+  const bool capped = max_dist < INFINITY;
+  // vertices whose list came back empty under the cap (reported on stderr and in --json; the stdout lines stay the reference's)
+  auto count_empty = [&](const std::vector<uint32_t>& ids, size_t rows) {
+    uint64_t e = 0;
+    for (size_t v = 0; v < rows; ++v) e += ids[v * (size_t)K] == PT_NOIDX ? 1 : 0;     // (lists are ascending: an empty row starts with PT_NOIDX)
+    return e;
+  };
   if (gpus != 0 || rank >= 0 || finalize) {
     // the sharded path (host/sharded.h): launcher -> one rank process per GPU -> finalize
     if (gpus < 1 || gpus > 64) { std::cerr << "--gpus must be in [1, 64]" << std::endl; return 2; }
     sharded::Options so;
     so.cloud = pc_file_name; so.mesh = mesh_file_name; so.out_name = out_name; so.tex_name = tex_name; so.rendezvous = rendezvous;
     so.K = K; so.device = device; so.mode = mode; so.ply_threads = ply_threads; so.resolution = resolution; so.pad = pad; so.gpus = gpus; so.rank = rank;
+    so.max_dist = max_dist;
     if (rank >= 0) return rank < gpus && !rendezvous.empty() ? sharded::run_rank(so) : 2;
     if (finalize) return rendezvous.empty() ? 2 : sharded::run_finalize(so, [&](const ply::FastMesh& m, const std::vector<float>& c, const std::vector<float>& n) { write_transfer_ply(out_name, m, c, n); });
     const auto t0 = clk::now();
@@ -176,6 +197,7 @@ int main(int argc, char** argv) {
     auto sdie = [&](const char* what) { std::cerr << "pointsTransfer: " << what << ": " << pt_last_error(sc) << std::endl; pt_ctx_destroy(sc); return 1; };
     pt_set_param(sc, "k_hint", (double)K);
     pt_set_param(sc, "sync", 1.0);
+    if (capped) pt_set_param(sc, "max_dist", max_dist);
     if (pt_build_synth(sc, syn_n, syn_seed, syn_dist, syn_type, -1, 0.0, 0.0) != PT_OK) return sdie("build failed");
     pt_stats_t st0;
     pt_stats(sc, &st0);
@@ -191,8 +213,10 @@ int main(int argc, char** argv) {
     t_task = clk::now();
     std::vector<uint32_t> idx(M * (size_t)K);
     std::vector<double> d2(M * (size_t)K);
-    std::vector<float> rgb(M * 3), nrm(M * 3);
+    std::vector<float> rgb(M * 3), nrm(M * 3);      // (zeros: what a generated target without a neighbour within --max-dist keeps)
     if (pt_query_resident_host(sc, K, mode, idx.data(), d2.data(), rgb.data(), nrm.data()) != PT_OK) return sdie("query failed");
+    const uint64_t syn_empty = capped ? count_empty(idx, M) : 0;
+    if (capped) std::cerr << "[pt_hip] " << syn_empty << " of " << M << " vertices have no point within " << max_dist << std::endl;
     pt_stats_t st;
     pt_stats(sc, &st);
     std::cout << "Neighbor search total time: " << since(t_task) << " seconds" << std::endl;
@@ -209,7 +233,9 @@ int main(int argc, char** argv) {
         << ", \"pt_stats\": {\"ms_build\": " << st.ms_build << ", \"ms_sort_targets\": " << st.ms_sort_targets << ", \"ms_query\": " << st.ms_query << ", \"grid_dim\": [" << st.grid_dim[0] << ", "
         << st.grid_dim[1] << ", " << st.grid_dim[2] << "], \"n_levels\": " << st.n_levels << ", \"pass1_pooled\": " << st.pass1_pooled << ", \"pass2_pooled\": " << st.pass2_pooled
         << ", \"uniform_probe\": " << st.uniform_probe << ", \"presort_refine\": " << st.presort_refine << ", \"n_sorts\": " << st.n_sorts << ", \"ordered_input\": " << st.ordered_input << ", \"n_leftover\": " << st.n_leftover << ", \"n_wave\": " << st.n_wave << ", \"device_bytes\": " << st.device_bytes
-        << ", \"targets_per_second_device\": " << (st.ms_build + st.ms_sort_targets + st.ms_query > 0 ? (double)M / ((st.ms_build + st.ms_sort_targets + st.ms_query) * 1e-3) : 0.0) << "}}\n";
+        << ", \"targets_per_second_device\": " << (st.ms_build + st.ms_sort_targets + st.ms_query > 0 ? (double)M / ((st.ms_build + st.ms_sort_targets + st.ms_query) * 1e-3) : 0.0) << "}";
+      if (capped) j << ", \"max_dist\": " << max_dist << ", \"vertices_without_neighbours\": " << syn_empty;
+      j << "}\n";
     }
     std::cout << "Output time: " << since(t_task) << " seconds" << std::endl;
     std::cout << "Total real time: " << since(t_total) << " seconds" << std::endl;
@@ -236,6 +262,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   pt_set_param(ctx, "k_hint", (double)K);
+  if (capped) pt_set_param(ctx, "max_dist", max_dist);
   ply::CloudSoA cloud;
   std::vector<void*> pinned;
   const bool pageable = std::getenv("PT_CLI_PAGEABLE") != nullptr;      // (measurement switch: plain malloc instead of page-locked memory)
@@ -290,6 +317,13 @@ int main(int argc, char** argv) {
   const double t_search = since(t_task);
   t_task = clk::now();
   std::vector<float> rgb(M * 3), nrm(M * 3);
+  uint64_t n_empty = 0;
+  if (capped) {
+    // a vertex with no point within --max-dist keeps its own colour and normal: the capped blend leaves such rows as it finds them
+    for (size_t v = 0; v < M; ++v)
+      for (int a = 0; a < 3; ++a) { rgb[3 * v + a] = (float)mesh.vertices[v].color[a]; nrm[3 * v + a] = (float)mesh.vertices[v].normal[a]; }
+    n_empty = count_empty(idx, M);
+  }
   rc = pt_blend(ctx, idx.data(), d2.data(), M, K, mode, rgb.data(), nrm.data());
   if (rc != PT_OK) { std::cerr << "pointsTransfer: blend failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
   const double t_blend = since(t_task);
@@ -336,9 +370,12 @@ int main(int argc, char** argv) {
       << ", \"n_refine\": " << st.n_refine << ", \"bbox_guess\": " << st.bbox_guess << ", \"pass1_pooled\": " << st.pass1_pooled << ", \"n_nodes\": " << st.n_nodes
       << ", \"n_leftover\": " << st.n_leftover << ", \"n_wave\": " << st.n_wave << ", \"device_bytes\": " << st.device_bytes << ", \"ms_kernel\": [";
     for (int i = 0; i < 8; ++i) j << (i ? ", " : "") << st.ms_kernel[i];
-    j << "]}}\n";
+    j << "]}";
+    if (capped) j << ", \"max_dist\": " << max_dist << ", \"vertices_without_neighbours\": " << n_empty;
+    j << "}\n";
     if (!j) std::cerr << "pointsTransfer: cannot write " << json_name << std::endl;
   }
+  if (capped) std::cerr << "[pt_hip] " << n_empty << " of " << M << " vertices have no point within " << max_dist << std::endl;
   if (pt_stats(ctx, &st) == PT_OK)
     std::cerr << "[pt_hip] grid " << st.grid_dim[0] << "x" << st.grid_dim[1] << "x" << st.grid_dim[2] << " cells, build " << st.ms_build
               << " ms, target sort " << st.ms_sort_targets << " ms, kNN " << st.ms_query << " ms, blend " << st.ms_blend << " ms, texture bake " << st.ms_bake << " ms (device time)"

@@ -53,6 +53,7 @@ namespace sharded {
 struct Options {
   std::string cloud, mesh, out_name = "transfer.ply", tex_name = "texture.png", rendezvous;
   int K = 20, device = 0, mode = PT_BLEND_MEAN, ply_threads = 0, resolution = 8192, pad = 25, gpus = 1, rank = -1;
+  double max_dist = INFINITY;       // --max-dist (every rank sets the same cap: pt_api.h "max_dist")
   bool finalize = false;
 };
 using clk = std::chrono::steady_clock;
@@ -193,6 +194,7 @@ inline int run_rank(const Options& o) {
     if (crc != PT_OK) return die("pt_comm_init");
   }
   pt_set_param(ctx, "k_hint", (double)o.K);
+  if (o.max_dist < INFINITY) pt_set_param(ctx, "max_dist", o.max_dist);
   // ---- cloud: this rank parses 1/world of the file and publishes the piece; the slab is then picked from all pieces --------------
   const double wait_s = 900.0;                   // (peers parse as long as this rank does -- a 1e9-point text cloud takes ~12 s per DESIGN 9; a peer that DIES ends the job through the launcher, this bound is for a launcher that was itself killed)
   long declared = 0;
@@ -288,6 +290,9 @@ inline int run_rank(const Options& o) {
   std::vector<uint32_t> idx(mh * (size_t)o.K);
   std::vector<double> d2(mh * (size_t)o.K);
   std::vector<float> rgb(mh * 3), nrm(mh * 3);
+  if (o.max_dist < INFINITY)        // a vertex with no point within the cap keeps its own colour and normal (the capped blend does not write its row)
+    for (size_t j = 0; j < mh; ++j)
+      for (int a = 0; a < 3; ++a) { rgb[3 * j + a] = (float)mesh.vertices[home[j]].color[a]; nrm[3 * j + a] = (float)mesh.vertices[home[j]].normal[a]; }
   pt_exchange_stats_t xs;
   if (pt_query_exchange_blend(ctx, txyz.data(), PT_F64, mh, o.K, axis, bounds.data(), o.mode, idx.data(), d2.data(), rgb.data(), nrm.data(), &xs) != PT_OK)
     return die("query / exchange failed");
@@ -371,6 +376,11 @@ inline int run_finalize(const Options& o, WritePly&& write_ply) {
                            o.pad, texture.data());
     if (rc != PT_OK) { std::cerr << "pointsTransfer: texture bake failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
     pt_ctx_destroy(ctx);
+  }
+  if (o.max_dist < INFINITY) {
+    uint64_t e = 0;
+    for (size_t v = 0; v < M; ++v) e += idx[v * K] == PT_NOIDX ? 1 : 0;
+    std::cerr << "[pt_hip] " << e << " of " << M << " vertices have no point within " << o.max_dist << std::endl;
   }
   std::cout << "Draw triangles total time: " << since(t_task) << " seconds" << std::endl;
   t_task = clk::now();

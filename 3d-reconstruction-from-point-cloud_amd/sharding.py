@@ -13,6 +13,9 @@ The reference is a single process; all of this is new design, fo
     north_star: "each GPU returning its local k candidates with an RCCL allgather over xGMI to merge";
   * (round 4) the attribute table may be SHARDED with the slabs (SlabAttributes): the answers then carry their
     candidates' records and the owner blends the completed rows from what it gathered -- per-GPU memory falls with G.
+  * a max_dist cap (PointsTransfer(max_dist=r) / set_param("max_dist", r)) is honoured by the GPU engine without anything here:
+    the native pack_requests takes min(k-th d2, r*r) as a target's reach and the bounded query answers within it.  Every rank
+    must set the same r.
 
 Collectives are torch.distributed all_gather (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).  The
 compute steps go through a small engine interface so that the CPU tests can drive the very same protocol code

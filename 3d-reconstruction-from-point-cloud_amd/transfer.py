@@ -46,7 +46,7 @@ def _ptr(a):
 class PointsTransfer:
     """One context = one GPU = one (slab of a) source cloud."""
 
-    def __init__(self, device=0, rho=None, k_hint=None):
+    def __init__(self, device=0, rho=None, k_hint=None, max_dist=None):
         self._L = capi.lib()
         self._h = C.c_void_p()
         dev = (C.c_int * 1)(device)
@@ -58,6 +58,21 @@ class PointsTransfer:
             self.set_param("k_hint", k_hint)      # cell density suited to the k the queries will use
         if rho is not None:
             self.set_param("rho", rho)
+        self._max_dist = math.inf
+        if max_dist is not None:
+            self.max_dist = max_dist
+
+    @property
+    def max_dist(self):
+        """Neighbours farther than this (cloud units) are not returned: their entries are (NOIDX, +inf), and blends leave a row without
+        any neighbour as the caller's output held it.  None / +inf = off (the default).  A query-time setting: no rebuild needed."""
+        return None if math.isinf(self._max_dist) else self._max_dist
+
+    @max_dist.setter
+    def max_dist(self, r):
+        r = math.inf if r is None else float(r)
+        self.set_param("max_dist", r)
+        self._max_dist = r
 
     # -- plumbing ------------------------------------------------------------------------
     def _chk(self, rc):
@@ -228,12 +243,16 @@ class PointsTransfer:
         return int(t.value)
 
     # -- blend / PCA ----------------------------------------------------------------------------
-    def blend(self, idx, d2=None, mode=capi.BLEND_MEAN):
+    def blend(self, idx, d2=None, mode=capi.BLEND_MEAN, rgb_out=None, nrm_out=None):
+        """rgb_out / nrm_out (optional float32 (m, 3) arrays): the outputs, filled in place and returned.  With max_dist set, a row
+        without any neighbour is not written -- it keeps what these arrays held (zeros when they are not given)."""
         idx = np.ascontiguousarray(idx, np.uint32)
         m, k = idx.shape
         d2c = None if d2 is None else np.ascontiguousarray(d2, np.float64)
-        rgb = np.empty((m, 3), np.float32)
-        nrm = np.empty((m, 3), np.float32)
+        rgb = np.zeros((m, 3), np.float32) if rgb_out is None else rgb_out
+        nrm = np.zeros((m, 3), np.float32) if nrm_out is None else nrm_out
+        assert rgb.dtype == np.float32 and rgb.shape == (m, 3) and rgb.flags.c_contiguous
+        assert nrm.dtype == np.float32 and nrm.shape == (m, 3) and nrm.flags.c_contiguous
         self._chk(self._L.pt_blend(self._h, _ptr(idx), _ptr(d2c), m, k, mode, _ptr(rgb), _ptr(nrm)))
         return rgb, nrm
 

@@ -151,7 +151,23 @@ int  pt_set_stream(pt_ctx*, void* hip_stream);
  * wave kernel takes what it leaves; 0, default: a wave per target -- measured faster), "local_ids" (1: the next slab build -- ascending
  * global indices, or a slab pt_build_synth generates -- keeps positions in its records and its own attribute records only; see
  * pt_set_attributes_local), "presort_refine" (1, default: the first build of a big cloud the sample finds non-uniform refines its cell size
- * from the sample's bound on the points per occupied cell, before the first sort; 0: after it, from the sort's count -- round 3's behaviour). */
+ * from the sample's bound on the points per occupied cell, before the first sort; 0: after it, from the sort's count -- round 3's behaviour).
+ *
+ * "max_dist" r (cloud units; r >= 0, +inf = off, the default; NaN or r < 0: PT_ERR_ARG): neighbours farther than r are not returned.
+ * R2 = r * r is computed once in double, and a source point is in reach iff d2 <= R2 (d2 the metric above; inclusive, like
+ * pt_query_bounded_dev).  Setting it needs no rebuild and keeps what the context learned for its next build.  While it is set:
+ *   - every query result (pt_query_aos / _soa, pt_query_resident / _blend_resident / _resident_host, pt_stream_query, and the
+ *     lists pt_exchange_merge_dev / _local / pt_query_exchange_blend complete) equals the uncapped result with every entry of
+ *     d2 > R2 replaced by (PT_NOIDX, +inf), bit for bit; pt_query_bounded_dev bounds each target by min(bound2[t], R2);
+ *   - pt_slab_need_dev, pt_pack_requests_dev and the exchange take min(d2[t][k-1], R2) as a target's reach (a short list reaches
+ *     only the slabs within r), and request packets carry that reach as their bound;
+ *   - the blends (pt_blend, pt_blend_dev, pt_query_blend_resident, pt_query_resident_host, pt_query_exchange_blend, the exchange's
+ *     re-blend) blend a row with at least one entry over the entries it has (mean over their count, or normalised inverse-d2), and do
+ *     NOT WRITE a row without any entry: rgb_out / nrm_out keep what the caller put there.  Uncapped, such rows get zeros, as ever.
+ *     pt_blend_weighted is unchanged;
+ *   - every context of a sharded job must use the same r: pt_exchange_merge_local returns PT_ERR_ARG when its contexts disagree, and
+ *     the ranks of an RCCL job (pt_exchange_merge_dev) must set the same value -- like "local_ids", nothing checks it across processes.
+ * pt_bake_texture takes the lists it is given (PT_NOIDX entries are skipped, as ever). */
 int  pt_set_param(pt_ctx*, const char* name, double value);
 const char* pt_last_error(pt_ctx*);
 int  pt_stats(pt_ctx*, pt_stats_t* out);
