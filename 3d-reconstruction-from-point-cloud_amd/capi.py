@@ -41,7 +41,12 @@ class Stats(C.Structure):
         ("n_nodes", C.c_uint32), ("refine_levels", C.c_int32), ("max_cell_points", C.c_uint32), ("n_wave", C.c_uint32),
         ("pass1_pooled", C.c_int32), ("stream_skipped", C.c_int32), ("stream_revisited", C.c_int32), ("pass2_pooled", C.c_int32),
         ("uniform_probe", C.c_int32), ("dup_leaves", C.c_int32), ("presort_refine", C.c_int32), ("n_sorts", C.c_int32), ("ordered_input", C.c_int32),
+        ("tile_variant", C.c_uint32 * 2), ("tile_retry_blocks", C.c_uint32), ("query_route", C.c_uint32),
     ]
+
+
+# pt_stats_t::query_route bits (include/pt_api.h)
+ROUTE_TILE, ROUTE_GROUP, ROUTE_GROUP_HIER, ROUTE_WAVE, ROUTE_WAVE_HIER, ROUTE_BLEND_LIST, ROUTE_BLEND_ALL = 1, 2, 4, 8, 16, 32, 64
 
 
 class ExchangeStats(C.Structure):

@@ -716,6 +716,7 @@ struct BlendReq { int mode; float* rgb_out; float* nrm_out; };
 // sort the resident targets into cell order and run the k-NN kernel
 int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const double* bound2_dev, uint32_t* idx_dev, double* d2_dev,
               const BlendReq* br = nullptr) {
+  c->st.tile_variant[0] = c->st.tile_variant[1] = 0u; c->st.tile_retry_blocks = 0u; c->st.query_route = 0u;
   if (!c->built) return fail(c, PT_ERR_STATE, "query before build");
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [1, %d]", k, PT_MAX_K);
   if (ttype != c->src_type) return fail(c, PT_ERR_UNSUPPORTED, "target xyz type %d differs from the source cloud's %d", ttype, c->src_type);
@@ -787,12 +788,12 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       HIPCHK(c, hipMemsetAsync(retry_n, 0, 4, c->stream));
       RES(c, c->retry, (size_t)c->gp.nblocks * sizeof(uint32_t));
     }
-    pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
+    c->st.tile_variant[0] = pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
                        tile_small, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr, blist, nlist,
                        second_chance ? (uint32_t*)c->retry.p : nullptr, retry_n, src64, tgt64, c->e_src, c->stream, bound2_dev, c->cap2);
     if (second_chance) {
       retry_launch = [=]() {
-        pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
+        c->st.tile_variant[1] = pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
                            0, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr,
                            (const uint32_t*)c->retry.p, c->h_counter[RB_RETRY], nullptr, nullptr, src64, tgt64, c->e_src, c->stream, bound2_dev, c->cap2);
       };
@@ -802,6 +803,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       // 0 blocks and no launch
       if (defer_retry) { retry_pending = true; return PT_OK; }
       HIPCHK(c, hipStreamSynchronize(c->stream));
+      c->st.tile_retry_blocks = c->h_counter[RB_RETRY];
       if (c->h_counter[RB_RETRY]) retry_launch();
     }
     return PT_OK;
@@ -849,6 +851,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
     using Rec = decltype(rec);
     const Rec* src = (const Rec*)c->rec.p;
     const uint32_t* cell_start = (const uint32_t*)c->cell_start.p;
+    auto note_wave = [&](const void* nodes, uint32_t count) { if (count) c->st.query_route |= nodes ? PT_ROUTE_WAVE_HIER : PT_ROUTE_WAVE; };
     // the two wave lists: plain variant for the first, descending variant for the second (every marked target is on one of them);
     // blend: the attributes are blended in the same launches
     auto wave_pair = [&](const Rec* tg, const double* bnd, bool blend) {
@@ -857,6 +860,8 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       const uint32_t nat = blend ? wnattr : 0;
       const int mode = blend ? wmode : 0;
       float *rgb = blend ? wrgb : nullptr, *nrm = blend ? wnrm : nullptr;
+      note_wave(nullptr, n1);
+      note_wave(c->nodes.p, n2);
       pt_launch_knn_wave<Rec>(c->gp, src, cell_start, nullptr, nullptr, 0xFFFFFFFFu, tg, n1, k, bnd, idx_dev, d2_dev, hlist, hcnt, c->stream, at, nat, mode, rgb, nrm);
       pt_launch_knn_wave<Rec>(c->gp, src, cell_start, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold, tg, n2, k, bnd,
                               idx_dev, d2_dev, hlist + n1, hcnt + 1, c->stream, at, nat, mode, rgb, nrm);
@@ -872,6 +877,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
             if (hipMemcpyAsync(c->h_counter + RB_WAVE_N, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
             if (retry_pending) {                              // the second-chance blocks' count came with it: their launch may add to the list
               retry_pending = false;
+              c->st.tile_retry_blocks = c->h_counter[RB_RETRY];
               if (c->h_counter[RB_RETRY]) {
                 retry_launch();
                 if (hipMemcpyAsync(c->h_counter + RB_WAVE_N, list_n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return;
@@ -880,6 +886,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
             cnt = c->h_counter[RB_WAVE_N];
           }
           c->st.n_wave = cnt;
+          note_wave(nullptr, cnt);
           pt_launch_knn_wave<Rec>(c->gp, src, cell_start, nullptr, nullptr, 0xFFFFFFFFu, tg, cnt, k, bnd, idx_dev, d2_dev, list, list_n, c->stream,
                                   wattr, wnattr, wmode, wrgb, wnrm);
           wave_blended = wattr != nullptr;
@@ -891,6 +898,7 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
         return;
       }
       if (wave) (void)hipMemsetAsync(heavy, 0, m, c->stream);
+      if (m) c->st.query_route |= hier ? PT_ROUTE_GROUP_HIER : PT_ROUTE_GROUP;
       if (hier) pt_launch_knn_hier<Rec>(c->gp, src, cell_start, (const uint32_t*)c->cell_node.p, (const uint32_t*)c->nodes.p, (uint32_t)c->refine_threshold, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
       else pt_launch_knn<Rec>(c->gp, src, cell_start, tg, m, k, bnd, idx_dev, d2_dev, list, list_n, c->stream, heavy, c->wave_min);
       if (wave && wave_lists()) wave_pair(tg, bnd, false);
@@ -905,13 +913,19 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       else r = tile_launches((const RecF*)c->rec32.p, nullptr, src, tsorted, todo_n);
       if (r != PT_OK) return r;
       group(tsorted, bnd_all, (const uint32_t*)c->todo.p, todo_n);       // (what the tile kernel left over keeps its bound, if it came with one)
-      if (br && !wave_blended)   // the targets the tile kernel handed over get their blend from the lists the group kernel just wrote
+      if (c->st.tile_variant[0]) c->st.query_route |= PT_ROUTE_TILE;
+      if (br && !wave_blended) {   // the targets the tile kernel handed over get their blend from the lists the group kernel just wrote
+        c->st.query_route |= PT_ROUTE_BLEND_LIST;
         pt_launch_blend_list<Rec>((const uint32_t*)c->todo.p, todo_n, m, tsorted, idx_dev, d2_dev, k, br->mode, (const Attr*)c->attr.p,
                                   (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream, capped);
+      }
       HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_TODO, todo_n, 4, hipMemcpyDeviceToHost, c->stream));
     } else {
       group(tsorted, bnd_all, nullptr, nullptr);
-      if (br && !wave_blended) pt_launch_blend(idx_dev, d2_dev, m, k, br->mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream, capped);
+      if (br && !wave_blended) {
+        c->st.query_route |= PT_ROUTE_BLEND_ALL;
+        pt_launch_blend(idx_dev, d2_dev, m, k, br->mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, br->rgb_out, br->nrm_out, c->stream, capped);
+      }
     }
     return PT_OK;
   });
@@ -1197,11 +1211,14 @@ int pt_build_soa_indexed(pt_ctx* c, const void* xyz, int xyz_type, const uint32_
   } else {
     int r = upload_xyz(c, c->in_xyz, xyz, xyz_type, n, on_device); if (r) return r;
   }
-  if (gidx) {
+  // an empty local-id slab is a local-id slab whatever gidx points to: a host's empty index vector may hand over nullptr (the CLI's
+  // `--gpus N` ranks whose slab holds no point), and its attribute table -- none of its own points -- still has to be accepted
+  const bool empty_local = c->want_local_ids && n == 0;
+  if (gidx || empty_local) {
     RES(c, c->in_gidx, std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-    { int r = copy_in(c, c->in_gidx.p, gidx, n * sizeof(uint32_t), on_device); if (r) return r; }
+    if (gidx) { int r = copy_in(c, c->in_gidx.p, gidx, n * sizeof(uint32_t), on_device); if (r) return r; }
   }
-  bool ascending = false;
+  bool ascending = empty_local;
   if (gidx && c->want_local_ids) {
     uint32_t* flag = (uint32_t*)c->counter.p + RB_ASCENDING;
     HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
@@ -1211,7 +1228,8 @@ int pt_build_soa_indexed(pt_ctx* c, const void* xyz, int xyz_type, const uint32_
     ascending = c->h_counter[RB_ASCENDING] == 0;
   }
   // a slab keeps the size of the attribute table it is indexed into (a whole cloud: its own); a refused local-id slab stays unbuilt
-  adopt_cloud(c, xyz_type, n, gidx ? c->n_total : n, !gidx ? IdMode::whole : (ascending ? IdMode::slab_local : IdMode::slab_global), keep_half, false);
+  adopt_cloud(c, xyz_type, n, gidx || empty_local ? c->n_total : n,
+              !gidx && !empty_local ? IdMode::whole : (ascending ? IdMode::slab_local : IdMode::slab_global), keep_half, false);
   if (gidx && c->want_local_ids && !ascending) return fail(c, PT_ERR_ARG, "local_ids: the slab's global indices must be strictly ascending (positions then order like indices)");
   return rebuild(c);
 }

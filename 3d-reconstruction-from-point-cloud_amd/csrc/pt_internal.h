@@ -105,11 +105,16 @@ void pt_launch_mark_near(const GridParams& gp, const Rec* tgt, const uint32_t* l
 void pt_launch_tblock_list(const uint32_t* tblock_start, uint32_t nblocks, uint32_t* list, uint32_t* count, hipStream_t s);
 constexpr int PT_TILE_CAP_SMALL_8 = 4400, PT_TILE_CAP_SMALL_16 = 3888, PT_TILE_CAP_LARGE = 8448, PT_TILE_CAP_WIDE = 8960;
 constexpr int PT_TILE_MAX_K = 32;      // beyond this the group kernel answers everything
-void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start,
-                        int k, uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr,
-                        int mode, float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry,
-                        uint32_t* retry_n, const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound = nullptr,
-                        double cap2 = INFINITY);   // bound (per target) and / or cap2 < +inf (max_dist squared): the bounded variants; with attr they blend too
+// the route code of one tile launch (pt_stats_t::tile_variant, include/pt_api.h): the instantiation's template arguments, packed
+#define PT_TILE_CODE(K, TWG, WIDE, BLEND, DBL, KC, BND, LISTED)                                                                          \
+  ((uint32_t)(K) | (uint32_t)(KC) << 6 | (uint32_t)((TWG) / 64) << 12 | (uint32_t)(bool)(WIDE) << 16 | (uint32_t)(bool)(BLEND) << 17 | \
+   (uint32_t)(bool)(DBL) << 18 | (uint32_t)(bool)(BND) << 19 | (uint32_t)(bool)(LISTED) << 20)
+// returns the launch's PT_TILE_CODE (0: no launch)
+uint32_t pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start,
+                            int k, uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr,
+                            int mode, float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry,
+                            uint32_t* retry_n, const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound = nullptr,
+                            double cap2 = INFINITY);   // bound (per target) and / or cap2 < +inf (max_dist squared): the bounded variants; with attr they blend too
 template <class T>
 void pt_launch_request_pack(const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g,
                             int my_slab, double cap2, uint32_t* count, uint32_t* sel, double* pkt, hipStream_t s);

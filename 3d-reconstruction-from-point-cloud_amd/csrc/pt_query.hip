@@ -2084,21 +2084,28 @@ template void pt_launch_knn_wave<RecD>(const GridParams&, const RecD*, const uin
 // blocks over the small budget but within the large one are listed there instead of going to `todo`; `blocks`: run over
 // such a list (nblocks_listed entries) instead of every block.  src_exact / tgt_exact (fp64 clouds): `src` is then the fp32
 // shadow of the sorted records and `tgt` is unused.
-void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start, int k,
-                        uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr, int mode,
-                        float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry, uint32_t* retry_n,
-                        const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound, double cap2) {
+// Returns the launch's route code (pt_stats_t::tile_variant, PT_TILE_CODE): taken from the template arguments of the instantiation the
+// macros below launch, so it cannot drift from the launch; 0 when nothing was launched.
+uint32_t pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start, int k,
+                            uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr, int mode,
+                            float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry, uint32_t* retry_n,
+                            const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound, double cap2) {
   const uint32_t nb = blocks ? nblocks_listed : (uint32_t)gp.nblocks;
-  if (!nb) return;
+  if (!nb) return 0u;
+  const bool listed = blocks != nullptr;
+  uint32_t code = 0u;
   const TileBlend bl{attr, n_attr, mode, rgb_out, nrm_out};
   const TileBlocks tbk{blocks, retry, retry_n, (uint32_t)PT_TILE_CAP_LARGE, bound, cap2};
   if (bound || cap2 < INFINITY) {
     // Bounded variants: per-target bounds (pt_stream_query's chunks; never with attr: the blended variants read cap2 only), the context's
     // max_dist (cap2), or both.  The
     // geometries are the unbounded launcher's below, medium one included; `attr` selects the fused blend (capped resident queries).
-#define PT_TILE_LAUNCHB1(KK, CAP, TH, WD, BL, DB, KCH)                                                                                                 \
-  hipLaunchKernelGGL((knn_tile_kernel<KK, CAP, TH, WD, BL, DB, KCH, true>), dim3(nb), dim3(TH), 0, s, gp, src, cell_start, tgt, tblock_start, k, \
-                     out_idx, out_d2, todo, todo_n, bl, tbk, TileDouble{src_exact, tgt_exact, e_src})
+#define PT_TILE_LAUNCHB1(KK, CAP, TH, WD, BL, DB, KCH)                                                                                                   \
+  do {                                                                                                                                             \
+    hipLaunchKernelGGL((knn_tile_kernel<KK, CAP, TH, WD, BL, DB, KCH, true>), dim3(nb), dim3(TH), 0, s, gp, src, cell_start, tgt, tblock_start, k, \
+                       out_idx, out_d2, todo, todo_n, bl, tbk, TileDouble{src_exact, tgt_exact, e_src});                                           \
+    code = PT_TILE_CODE(KK, TH, WD, BL, DB, KCH, true, listed);                                                                                    \
+  } while (0)
 #define PT_TILE_LAUNCHB(KK, CAP, TH, WD, KCH)                                 \
   do {                                                                        \
     if (src_exact) {                                                          \
@@ -2124,12 +2131,15 @@ void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* c
     }
 #undef PT_TILE_LAUNCHB
 #undef PT_TILE_LAUNCHB1
-    return;
+    return code;
   }
   const TileDouble dd{src_exact, tgt_exact, e_src};
-#define PT_TILE_LAUNCH1(KK, CAP, TH, WD, BL, DB, KCH)                                                                                             \
-  hipLaunchKernelGGL((knn_tile_kernel<KK, CAP, TH, WD, BL, DB, KCH>), dim3(nb), dim3(TH), 0, s, gp, src, cell_start, tgt, tblock_start, k, out_idx, \
-                     out_d2, todo, todo_n, bl, tbk, dd)
+#define PT_TILE_LAUNCH1(KK, CAP, TH, WD, BL, DB, KCH)                                                                                               \
+  do {                                                                                                                                         \
+    hipLaunchKernelGGL((knn_tile_kernel<KK, CAP, TH, WD, BL, DB, KCH>), dim3(nb), dim3(TH), 0, s, gp, src, cell_start, tgt, tblock_start, k, out_idx, \
+                       out_d2, todo, todo_n, bl, tbk, dd);                                                                                     \
+    code = PT_TILE_CODE(KK, TH, WD, BL, DB, KCH, false, listed);                                                                               \
+  } while (0)
 #define PT_TILE_LAUNCHC(KK, CAP, TH, WD, KCH)                             \
   do {                                                                    \
     if (src_exact) {                                                      \
@@ -2158,12 +2168,12 @@ void pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* c
     else if (k <= 20) PT_TILE_LAUNCHC(32, PT_TILE_CAP_LARGE, 768, false, 20);       // the reference's K = 20 (src/pointsTransfer.cpp:128): a chain of exactly 20
     // (round 3: the same body on 1024 threads -- 16 waves per CU, 128 VGPRs with 56 bytes of spills, 7680-record region -- measured 6.77 ms
     //  against 6.74 at 100M / 10M: more waves of one workgroup do not shorten its latency chain)
-    else if (k <= 24) PT_TILE_LAUNCHC(32, PT_TILE_CAP_LARGE, 768, false, 24);
-    else PT_TILE_LAUNCH(32, PT_TILE_CAP_LARGE, 768, false);
+    else PT_TILE_LAUNCHC(32, PT_TILE_CAP_LARGE, 768, false, 24);      // (k in 25..32 took the wide branch above)
   }
 #undef PT_TILE_LAUNCH
 #undef PT_TILE_LAUNCHC
 #undef PT_TILE_LAUNCH1
+  return code;
 }
 
 // pt_stream_query, once per chunk and sweep: the bound every target brings to this chunk's search, and how many targets bring one that

@@ -110,7 +110,26 @@ typedef struct pt_stats_t {
                              * pooled pass had to be redone) */
   int32_t ordered_input;    /* last build: 1 = the sample found the cloud stored in spatial order (of 64 consecutive points most share a block): regions and
                              * cell size are then not taken from a sample */
+  /* The route of the last query (of pt_stream_query: its last searched chunk; of the exchange: its last search), reset by every query
+   * and valid whether "sync" is set or not -- none of them needs a read-back the query does not make anyway. */
+  uint32_t tile_variant[2]; /* the LDS tile kernel's instantiation: [0] its first launch, [1] the large-geometry retry launch over the blocks the
+                             * two-per-CU geometry passed on; 0 = no such launch.  Bits (PT_TILE_CODE in csrc/pt_internal.h): 0-5 K (the list
+                             * width: 8, 16, 32), 6-11 KC (the pass-1 chain), 12-15 threads per workgroup / 64, 16 WIDE queue, 17 BLEND (fused
+                             * blend), 18 DBL (fp64 cloud: fp32 shadow, exact records in pass 3), 19 BND (per-target bounds and / or the cap),
+                             * 20 the launch ran over a list of blocks (tile_sparse, or the retry) */
+  uint32_t tile_retry_blocks; /* blocks the retry launch took (0: none, or no two-per-CU geometry ran) */
+  uint32_t query_route;     /* PT_ROUTE_* bits: the kernels the last query launched (a launch over a device-side list counts even when the list
+                             * turns out empty -- its length stays on the device) */
 } pt_stats_t;
+enum {
+  PT_ROUTE_TILE = 1,        /* the LDS tile kernel */
+  PT_ROUTE_GROUP = 2,       /* the 8-lanes-per-target kernel, plain */
+  PT_ROUTE_GROUP_HIER = 4,  /* ... the variant that descends into refined cells */
+  PT_ROUTE_WAVE = 8,        /* the one-wave-per-target kernel, plain */
+  PT_ROUTE_WAVE_HIER = 16,  /* ... the variant that descends into refined cells */
+  PT_ROUTE_BLEND_LIST = 32, /* a blend pass over the rows the tile kernel handed over (fused queries) */
+  PT_ROUTE_BLEND_ALL = 64   /* a blend pass over every row (fused queries the tile kernel did not take) */
+};
 
 /* ---- context ------------------------------------------------------------------------ */
 /* device_ids[0] is the GPU this context runs on (one process per GPU); n_devices must be 1. */

@@ -120,11 +120,21 @@ def test_product_never_imports_the_oracle():
     assert not bad, "product files reference the oracle: %s" % bad
 
 
+_ASM = []
+
+
+def _query_asm():
+    """the device assembly of csrc/pt_query.hip (`make asm`), built once per session"""
+    if not _ASM:
+        subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "-s", "asm"])
+        _ASM.append(open(os.path.join(PKG, "csrc", "_build", "asm", "pt_query-hip-amdgcn-amd-amdhsa-gfx950.s")).read())
+    return _ASM[0]
+
+
 def test_metric_has_no_fma_in_query_kernels():
     """reference src/Distance.h:6-11 compiles to 3 mul + 2 add under the reference's flags (SURVEY.md 7.3);
     the HIP query kernels must not contract it (hipcc defaults to -ffp-contract=fast)."""
-    subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "-s", "asm"])
-    s = open(os.path.join(PKG, "csrc", "_build", "asm", "pt_query-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    s = _query_asm()
     assert "knn_kernel" in s and "v_mul_f64" in s and "v_add_f64" in s
     # per kernel body; the tile kernel's BLEND = true instantiations (last but one template argument) are the
     # same metric code plus an epilogue whose fp64 divisions and sqrt expand to FMA sequences -- those are skipped
@@ -157,6 +167,87 @@ def test_metric_has_no_fma_in_query_kernels():
         # k-NN + blend tile kernel: 36 bytes, 16 lane writes at entry).
         lane_spill_only = (not touches) and int(m.group(1)) <= 64 and "SGPR spill to VGPR lane" in b
         assert int(m.group(1)) == 0 or lane_spill_only or (hier and int(m.group(1)) <= 512) or (wave and int(m.group(1)) <= 64), (name, m.group(1))
+
+
+_TILE_RE = re.compile(r"knn_tile_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELb([01])ELb([01])ELi(\d+)ELb([01])EE")
+
+
+def test_tile_variant_table_equals_the_compiled_instantiations():
+    """tests/_tile_variants.py names every knn_tile_kernel<K, CAP, TWG, WIDE, BLEND, DBL, KC, BND> the compiler emitted, and nothing
+    else: an instantiation without a row (or a row without an instantiation) fails here, so the GPU matrix that runs every row covers
+    every variant that can answer a query."""
+    import _tile_variants as TV
+    s = _query_asm()
+    compiled = set()
+    for b in s.split("; -- Begin function ")[1:]:
+        name = b.split("\n", 1)[0].strip()
+        if "knn_tile_kernel" not in name:
+            continue
+        m = _TILE_RE.search(name)
+        assert m, "an instantiation the decoder does not understand: %s" % name
+        g = m.groups()
+        compiled.add((int(g[0]), int(g[1]), int(g[2]), g[3] == "1", g[4] == "1", g[5] == "1", int(g[6]), g[7] == "1"))
+    table = [TV.instantiation(r) for r in TV.ROWS]
+    assert len(table) == len(set(table)), "a row is listed twice"
+    assert not compiled - set(table), "compiled but not in tests/_tile_variants.py: %s" % sorted(compiled - set(table))
+    assert not set(table) - compiled, "in tests/_tile_variants.py but not compiled: %s" % sorted(set(table) - compiled)
+    assert len(compiled) == 72
+    # the route codes tell every row apart, and decode to the row's template arguments
+    assert len({TV.row_code(r) for r in TV.ROWS}) == len(TV.ROWS)
+    for r in TV.ROWS:
+        d = TV.decode(TV.row_code(r))
+        assert (d["K"], d["TWG"], d["WIDE"], d["BLEND"], d["DBL"], d["KC"], d["BND"], d["listed"]) == \
+            (r["K"], r["TWG"], r["WIDE"], r["BLEND"], r["DBL"], r["KC"], r["BND"], False)
+
+
+def _c_struct_members(txt, name):
+    """member names of `typedef struct name { ... } name;` in a C header, in declaration order (arrays: the name alone)"""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), txt, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if not decl:
+            continue
+        first, *rest = decl.split(",")
+        for d in [first.split()[-1]] + [r.strip() for r in rest]:
+            names.append(re.sub(r"\[.*\]", "", d).lstrip("*"))
+    return names
+
+
+def test_python_mirrors_of_the_c_structs(tmp_path, pkg):
+    """capi.Stats, capi.ExchangeStats and transfer.POINT_DTYPE have the sizes and field offsets of pt_stats_t, pt_exchange_stats_t and
+    pt_point as a C compiler lays them out (pt_stats writes sizeof(pt_stats_t) bytes into the Python buffer)."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "pt_api.h")).read()
+    structs = {"pt_stats_t": pkg.capi.Stats, "pt_exchange_stats_t": pkg.capi.ExchangeStats, "pt_point": None}
+    members = {s: _c_struct_members(hdr, s) for s in structs}
+    src = ["#include <stdio.h>", "#include <stddef.h>", "#include \"pt_api.h\"", "int main(void) {"]
+    for s, ms in members.items():
+        src.append('  printf("%s sizeof %%zu\\n", sizeof(%s));' % (s, s))
+        for f in ms:
+            src.append('  printf("%s %s %%zu\\n", offsetof(%s, %s));' % (s, f, s, f))
+    src += ["  return 0;", "}"]
+    (tmp_path / "abi.c").write_text("\n".join(src) + "\n")
+    exe = str(tmp_path / "abi")
+    subprocess.check_call(["gcc", "-std=c11", "-I" + os.path.join(ROOT, "include"), "-o", exe, str(tmp_path / "abi.c")])
+    got = {}
+    for line in subprocess.check_output([exe], text=True).splitlines():
+        s, f, v = line.split()
+        got.setdefault(s, {})[f] = int(v)
+    for s, cls in structs.items():
+        if cls is None:
+            continue
+        names = [f[0] for f in cls._fields_]
+        assert names == members[s], "%s: the Python mirror's fields %s differ from the header's %s" % (s, names, members[s])
+        assert C.sizeof(cls) == got[s]["sizeof"], "%s: sizeof %d in C, %d in Python" % (s, got[s]["sizeof"], C.sizeof(cls))
+        for f in names:
+            assert getattr(cls, f).offset == got[s][f], "%s.%s: offset %d in C, %d in Python" % (s, f, got[s][f], getattr(cls, f).offset)
+    dt = pkg.POINT_DTYPE
+    assert dt.itemsize == got["pt_point"]["sizeof"]
+    assert [n for n in members["pt_point"] if not n.startswith("_pad")] == list(dt.names)
+    for n in dt.names:
+        assert dt.fields[n][1] == got["pt_point"][n], "pt_point.%s" % n
 
 
 def test_png_writer_roundtrip(tmp_path):

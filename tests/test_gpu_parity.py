@@ -1444,6 +1444,19 @@ def test_streamed_source_100m_equals_resident(pkg, oracle):
 @pytest.mark.parametrize("g,k,f64,sharded", [(2, 8, False, False), (3, 20, True, False), (5, 8, False, False), (2, 8, False, True), (3, 20, True, True), (5, 16, False, True),
                                              (8, 8, False, True), (8, 20, True, False)])
 def test_native_exchange_on_logical_slabs(pkg, oracle, g, k, f64, sharded):
+    _native_exchange(pkg, oracle, g, k, f64, sharded)
+
+
+@pytest.mark.parametrize("sharded", [False, True])
+def test_native_exchange_with_an_empty_slab(pkg, oracle, sharded):
+    """The same with a slab that holds no source point (a tiny cloud, or many points on one coordinate of the cut axis), built the way
+    the ranks of `pointsTransfer --gpus N` build it: pt_build_soa_indexed(xyz = NULL, gidx = NULL, n = 0) and, in local-id mode,
+    pt_set_attributes_local(NULL, NULL).  Its home targets start from empty lists; the exchange completes them."""
+    _native_exchange(pkg, oracle, 3, 8, False, sharded, empty=True)
+    _native_exchange(pkg, oracle, 3, 20, True, sharded, empty=True)
+
+
+def _native_exchange(pkg, oracle, g, k, f64, sharded, empty=False):
     """G contexts of one process, one slab each (equal-count quantiles along x; the last slab may hold NO targets): home search,
     then pt_exchange_merge_local -- count matrix, owner-to-owner requests, bounded answers, merge, re-blend of the completed rows.
     Result: the global search bit for bit, and the blend of every row within 1e-5 of the oracle's.
@@ -1457,23 +1470,36 @@ def test_native_exchange_on_logical_slabs(pkg, oracle, g, k, f64, sharded):
     tgt = tgt[:, tgt[0] < 0.93]                                              # nothing homed near the far end: an empty last rank at g = 5
     m = tgt.shape[1]
     rgb, nrm = oracle.synth_rgb(seed, n), oracle.synth_nrm(seed, n)
+    if empty:                                                                # no source in [0.5, 0.502): the middle one of three slabs
+        keep = ~((src[0] >= 0.5) & (src[0] < 0.502))
+        src = np.ascontiguousarray(src[:, keep]); rgb = rgb[keep]; nrm = nrm[keep]
     want_i, want_d = oracle.KdTree(src.astype(np.float64)).query(tgt.astype(np.float64), k)
     bounds = [-math.inf] + [float(v) for v in np.quantile(src[0], np.arange(1, g) / g)] + [math.inf]
     if g == 5:
         bounds[-2] = 0.95
+    if empty:
+        bounds = [-math.inf, 0.5, 0.502, math.inf]
     home = np.clip(np.searchsorted(np.array(bounds), tgt[0], side="right") - 1, 0, g - 1)
+    assert not empty or (home == 1).any()
     pts, xs, ii, dd, cc, nn, rows = [], [], [], [], [], [], []
     for s in range(g):
         p = pkg.PointsTransfer(device=0, k_hint=k)
         sel = np.nonzero((src[0] >= bounds[s]) & (src[0] < bounds[s + 1]))[0]
         if sharded:
             p.set_param("local_ids", 1)
-        p.build(np.ascontiguousarray(src[:, sel]), gidx=sel.astype(np.uint32))
-        if sharded:
+        if empty and len(sel) == 0:                                          # the CLI's empty slab: its empty vectors hand over null pointers
+            assert p._L.pt_build_soa_indexed(p._h, None, xt, None, 0, 0) == 0, p._L.pt_last_error(p._h)
+            if sharded:
+                assert p._L.pt_set_attributes_local(p._h, None, None, 0) == 0, p._L.pt_last_error(p._h)
+            else:
+                p.set_attributes(rgb, nrm)
+        elif sharded:
+            p.build(np.ascontiguousarray(src[:, sel]), gidx=sel.astype(np.uint32))
             p.set_attributes_local(rgb[sel], nrm[sel])                       # this slab's points only: 1 / g of the table
             with pytest.raises(pkg.PtError):
                 p.set_attributes(rgb, nrm)
         else:
+            p.build(np.ascontiguousarray(src[:, sel]), gidx=sel.astype(np.uint32))
             p.set_attributes(rgb, nrm)                                       # the table is replicated: indexed by the global index
         mine = np.nonzero(home == s)[0]
         ms = len(mine)
@@ -1499,6 +1525,34 @@ def test_native_exchange_on_logical_slabs(pkg, oracle, g, k, f64, sharded):
     assert np.abs(gc - rc).max() / 255.0 <= TOL and np.abs(gn - rn).max() <= TOL
     for p in pts:
         p.close()
+
+
+def test_empty_local_id_slab(pkg):
+    """A local-id slab with no point, built as the ranks of `pointsTransfer --gpus N` build it (xyz = gidx = NULL, n = 0: what an empty
+    vector's data() gives): the build and the upload of its (empty) attribute table succeed, queries return (NOIDX, +inf) rows, and a
+    fused blend writes zeros to those rows -- or, capped, leaves them as the caller's outputs held them."""
+    import torch
+    m, k = 40, 8
+    tgt = np.random.default_rng(3).random((3, m))
+    with pkg.PointsTransfer(device=0) as p:
+        L = p._L
+        p.set_param("local_ids", 1)
+        assert L.pt_build_soa_indexed(p._h, None, pkg.F64, None, 0, 0) == pkg.capi.OK, L.pt_last_error(p._h)
+        assert p.num_source == 0
+        assert L.pt_set_attributes_local(p._h, None, None, 0) == pkg.capi.OK, L.pt_last_error(p._h)
+        gi, gd = p.query(tgt, k)
+        assert (gi == pkg.NOIDX).all() and np.isinf(gd).all()
+        p.set_targets(tgt)
+        for cap in (None, 1.0):
+            p.max_dist = cap
+            sc = np.full((m, 3), 5.0, np.float32); sn = np.full((m, 3), -2.0, np.float32)
+            i_ = torch.empty((m, k), dtype=torch.int32, device="cuda"); d_ = torch.empty((m, k), dtype=torch.float64, device="cuda")
+            c_ = torch.from_numpy(sc.copy()).cuda(); n_ = torch.from_numpy(sn.copy()).cuda()
+            p.query_blend_resident_dev(k, pkg.BLEND_MEAN, i_, d_, c_, n_)
+            torch.cuda.synchronize()
+            assert (i_.cpu().numpy().view(np.uint32) == pkg.NOIDX).all() and np.isinf(d_.cpu().numpy()).all()
+            want_c, want_n = (sc, sn) if cap else (np.zeros_like(sc), np.zeros_like(sn))
+            assert np.array_equal(c_.cpu().numpy(), want_c) and np.array_equal(n_.cpu().numpy(), want_n), "cap %s" % cap
 
 
 def test_local_id_slab_matches_the_global_id_slab(pkg, oracle):
@@ -1753,6 +1807,32 @@ def test_cli_sharded_path(tmp_path, pkg, oracle, gpus, fmt):
     parsed = sorted(tuple(int(v) for v in re.findall(r"parsed records \[(\d+), (\d+)\) of (\d+)", l)[0]) for l in r2.stderr.splitlines() if "parsed records" in l)
     assert len(parsed) == gpus and parsed[0][0] == 0 and parsed[-1][1] == parsed[-1][2] == src.shape[1]
     assert all(parsed[i][1] == parsed[i + 1][0] for i in range(gpus - 1))
+
+
+def test_cli_sharded_path_with_an_empty_slab(tmp_path, pkg):
+    """`pointsTransfer ... --gpus 2` on a cloud whose cut leaves rank 0 with no point: 60 % of the points share the lowest coordinate
+    of the cut axis (y, the longest within 10 %), so the median -- the slab bound -- is that coordinate and slab 0 (y below it) is
+    empty.  That rank builds from empty vectors (null pointers, n = 0) and must take part in the exchange like the others: the outputs
+    equal the single-process run's.  Needs two GPUs."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs 2 GPUs: this box shows %d" % torch.cuda.device_count())
+    from _bake_cases import make_case
+    src, rgb, verts, uv, vrgb, faces = make_case(17, n=3000, grid=4)
+    src[1, :1800] = 0.0
+    pc, mesh = tmp_path / "cloud.ply", tmp_path / "mesh.ply"
+    _write_binary_plys(pc, mesh, src, rgb, verts, uv, vrgb, faces)
+    exe = os.path.join(os.path.dirname(pkg.capi.LIB_PATH), "pointsTransfer")
+    d1, d2_ = tmp_path / "single", tmp_path / "sharded"
+    d1.mkdir(); d2_.mkdir()
+    r1 = subprocess.run([exe, str(pc), str(mesh), "--resolution", "400"], capture_output=True, text=True, cwd=d1)
+    r2 = subprocess.run([exe, str(pc), str(mesh), "--resolution", "400", "--gpus", "2"], capture_output=True, text=True, cwd=d2_, timeout=300)
+    assert r1.returncode == 0 and r2.returncode == 0, r1.stderr + r2.stderr
+    assert re.search(r"\[pt_hip rank 0\] slab 0 points", r2.stderr), r2.stderr
+    assert np.array_equal(_read_png_rgba(d1 / "texture.png"), _read_png_rgba(d2_ / "texture.png"))
+    rows = lambda d: np.array([[float(v) for v in l.split()] for l in open(d / "transfer.ply").read().split("end_header\n")[1].strip().splitlines()[:verts.shape[1]]])
+    a, b = rows(d1), rows(d2_)
+    assert np.abs(a[:, 8:] - b[:, 8:]).max() <= 1 and np.abs(a[:, :8] - b[:, :8]).max() <= 2e-5
 
 
 # ---- refined cells (pt_refine.hip): sub-grids inside heavy cells, descended into by the group kernel ---------------------------
