@@ -72,9 +72,11 @@ __device__ inline void draw_triangle(const double (&U)[3], const double (&V)[3],
   if (!(A != 0.0) || !finite_d(A)) return;
   const double xmin = fmin(px, fmin(qx, rx)), xmax = fmax(px, fmax(qx, rx));
   const double ymin = fmin(py, fmin(qy, ry)), ymax = fmax(py, fmax(qy, ry));
-  const int i0 = (int)fmax(floor(xmin), 0.0), i1 = (int)fmin(floor(xmax), (double)(R - 1));      // column i in [0, R)
-  const int j0 = (int)fmax(floor(ymin), 1.0), j1 = (int)fmin(floor(ymax), (double)R);            // row R - j in [0, R)
-  if (i1 < i0 || j1 < j0) return;
+  const double fi0 = floor(xmin), fi1 = floor(xmax), fj0 = floor(ymin), fj1 = floor(ymax);
+  // a bounding box wholly outside the texture is rejected in double, so that every cast below sees a value in [0, R]
+  if (fi1 < 0.0 || fi0 > (double)(R - 1) || fj1 < 1.0 || fj0 > (double)R) return;
+  const int i0 = (int)fmax(fi0, 0.0), i1 = (int)fmin(fi1, (double)(R - 1));                      // column i in [0, R)
+  const int j0 = (int)fmax(fj0, 1.0), j1 = (int)fmin(fj1, (double)R);                            // row R - j in [0, R)
   const unsigned long long ni = (unsigned long long)(i1 - i0 + 1), total = ni * (unsigned long long)(j1 - j0 + 1);
   for (unsigned long long pix = (unsigned long long)lane; pix < total; pix += 64ull) {
     const int i = i0 + (int)(pix % ni), j = j0 + (int)(pix / ni);

@@ -67,6 +67,7 @@ def lib():
         L.pto_blend_weighted.argtypes = [p, p, u64, i32, p, p, p, p]
         L.pto_pca_normals.argtypes = [p, u64, i32, p, u64, p, p, p]
         L.pto_bake_texture.argtypes = [p, p, u64, p, p, p, u64, p, u64, p, i32, i32, p]
+        L.pto_bake_face_report.argtypes = [p, p, u64, p, p, p, u64, p, u64, p, i32, u64, p]
         L.pto_dilate_pad.argtypes = [p, i32, i32, p]
         _lib = L
     return _lib
@@ -250,6 +251,37 @@ def bake_texture(src_xyz, src_rgb, vert_xyz, vert_uv, vert_rgb, faces, nbr_idx, 
                                 resolution, _ptr(out))
     assert rc == 0
     return out
+
+
+_MAXPTS, _MAXTRI = 99, 255
+
+
+class _BakeFace(C.Structure):
+    """pto_bake_face of pt_oracle.c"""
+    _fields_ = [("valid", C.c_int32), ("frame_ok", C.c_int32), ("nid", C.c_int32), ("ninside", C.c_int32), ("np", C.c_int32), ("ntri", C.c_int32),
+                ("ntri_all", C.c_int64), ("px", C.c_double * _MAXPTS), ("py", C.c_double * _MAXPTS), ("pu", C.c_double * _MAXPTS),
+                ("pv", C.c_double * _MAXPTS), ("pid", C.c_uint32 * _MAXPTS), ("pc", C.c_uint8 * (3 * _MAXPTS)), ("tri", C.c_uint8 * (3 * _MAXTRI))]
+
+
+def bake_face_report(src_xyz, src_rgb, vert_xyz, vert_uv, vert_rgb, faces, nbr_idx, face):
+    """What pto_bake_texture makes of face number `face` before it draws (same arguments as bake_texture, no resolution): a dict with
+    valid, frame_ok, nid (distinct list entries < n), ninside, np (kept points, corners included), ntri, xy / uv (np, 2), rgb (np, 3),
+    ids (np,; NOIDX for the corners), tris (ntri, 3) -- the accepted triples in drawing order, at most 255 -- and ntri_all, the
+    uncapped number of empty-circle triples."""
+    sx = _planar64(src_xyz); vx = _planar64(vert_xyz)
+    srgb = np.ascontiguousarray(src_rgb, np.uint8); vrgb = np.ascontiguousarray(vert_rgb, np.uint8)
+    uv = np.ascontiguousarray(vert_uv, np.float64); fc = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    nb = np.ascontiguousarray(nbr_idx, np.uint32)
+    F = _BakeFace()
+    rc = lib().pto_bake_face_report(_ptr(sx), _ptr(srgb), sx.shape[1], _ptr(vx), _ptr(uv), _ptr(vrgb), vx.shape[1], _ptr(fc), fc.shape[0], _ptr(nb), nb.shape[1],
+                                    face, C.byref(F))
+    assert rc == C.sizeof(F), "pto_bake_face layout: C says %d bytes, ctypes %d" % (rc, C.sizeof(F))
+    m, t = F.np, F.ntri
+    return dict(valid=bool(F.valid), frame_ok=bool(F.frame_ok), nid=F.nid, ninside=F.ninside, np=m, ntri=t, ntri_all=F.ntri_all,
+                xy=np.stack([np.array(F.px[:m]), np.array(F.py[:m])], axis=1).reshape(m, 2),
+                uv=np.stack([np.array(F.pu[:m]), np.array(F.pv[:m])], axis=1).reshape(m, 2),
+                rgb=np.array(F.pc[:3 * m], np.uint8).reshape(m, 3), ids=np.array(F.pid[:m], np.uint32),
+                tris=np.array(F.tri[:3 * t], np.int64).reshape(t, 3))
 
 
 def dilate_pad(bgra, ksize=25):

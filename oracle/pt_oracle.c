@@ -672,7 +672,9 @@ static void pto_draw_triangle(const double* U, const double* V, const uint8_t (*
   double xmin = fmin(p.x, fmin(q.x, r.x)), xmax = fmax(p.x, fmax(q.x, r.x));
   double ymin = fmin(p.y, fmin(q.y, r.y)), ymax = fmax(p.y, fmax(q.y, r.y));
   double fi0 = floor(xmin), fi1 = floor(xmax), fj0 = floor(ymin), fj1 = floor(ymax);
-  /* only pixels that land inside the texture: col i in [0, R), row R - j in [0, R) <=> j in [1, R] */
+  /* only pixels that land inside the texture: col i in [0, R), row R - j in [0, R) <=> j in [1, R].  A bounding box wholly outside
+   * is rejected in double, so that every cast below sees a value in [0, R] (a double beyond the int range has no defined cast) */
+  if (fi1 < 0.0 || fi0 > (double)(R - 1) || fj1 < 1.0 || fj0 > (double)R) return;
   const int i0 = (int)fmax(fi0, 0.0), i1 = (int)fmin(fi1, (double)(R - 1));
   const int j0 = (int)fmax(fj0, 1.0), j1 = (int)fmin(fj1, (double)R);
   for (int i = i0; i <= i1; ++i)
@@ -710,84 +712,127 @@ static inline int in_circumcircle(const v2* P, int i, int j, int k, int l, int o
   else { d = incircle_sorted(P, l, i, j, k); par = -1; }
   return (double)(os * par) * d > 0.0;
 }
+/* What the bake makes of one face before it draws: the report the tests read, and the struct pto_bake_texture draws from. */
+typedef struct {
+  int32_t valid;                        /* 0: malformed face (an index negative or >= nv), nothing else is filled */
+  int32_t frame_ok;                     /* the plane frame and the face's 2-D area are finite and non-zero */
+  int32_t nid;                          /* distinct neighbour indices < n in the three lists */
+  int32_t ninside;                      /* of those, inside the face (all three barycentrics >= 0) */
+  int32_t np;                           /* kept points: 3 corners + inside points with a 2-D image of their own */
+  int32_t ntri;                         /* triangles drawn: min(ntri_all, 255); 0 when np == 3 (the plain face is drawn) */
+  int64_t ntri_all;                     /* empty-circle triples found, uncapped */
+  double px[PTO_BAKE_MAXPTS], py[PTO_BAKE_MAXPTS];      /* 2-D images, corners first */
+  double pu[PTO_BAKE_MAXPTS], pv[PTO_BAKE_MAXPTS];      /* UVs */
+  uint32_t pid[PTO_BAKE_MAXPTS];        /* source index of a kept point (PTO_NOIDX for the corners) */
+  uint8_t pc[PTO_BAKE_MAXPTS][3];       /* colours r, g, b */
+  uint8_t tri[255][3];                  /* accepted triples i < j < k in enumeration order */
+} pto_bake_face;
+
+static void pto_bake_one_face(const double* src_xyz, const uint8_t* src_rgb, uint64_t n, const double* vert_xyz, const double* vert_uv,
+                              const uint8_t* vert_rgb, uint64_t nv, const int32_t* fv, const uint32_t* nbr_idx, int k, pto_bake_face* F) {
+  memset(F, 0, sizeof *F);
+  if (fv[0] < 0 || fv[1] < 0 || fv[2] < 0 || (uint64_t)fv[0] >= nv || (uint64_t)fv[1] >= nv || (uint64_t)fv[2] >= nv) return;   /* malformed face: skipped */
+  F->valid = 1;
+  double cu[3], cv[3], c3[3][3];
+  for (int c = 0; c < 3; ++c) {
+    cu[c] = vert_uv[2 * (size_t)fv[c]]; cv[c] = vert_uv[2 * (size_t)fv[c] + 1];
+    for (int a = 0; a < 3; ++a) { c3[c][a] = vert_xyz[(size_t)a * nv + (size_t)fv[c]]; F->pc[c][a] = vert_rgb[3 * (size_t)fv[c] + a]; }
+  }
+  /* union of the three corners' neighbour lists by original index, ascending (:470-479) */
+  uint32_t ids[96]; int nid = 0;
+  for (int c = 0; c < 3; ++c)
+    for (int j = 0; j < k; ++j) { const uint32_t id = nbr_idx[(size_t)fv[c] * k + j]; if (id != PTO_NOIDX && id < n) ids[nid++] = id; }
+  qsort(ids, (size_t)nid, sizeof(uint32_t), cmp_u32);
+  { int w = 0; for (int j = 0; j < nid; ++j) if (j == 0 || ids[j] != ids[j - 1]) ids[w++] = ids[j]; nid = w; }
+  F->nid = nid;
+  /* plane frame (:485-494): origin corner 0, e1 along corner0 -> corner1, e2 = n x e1, both unit */
+  const double ax = c3[1][0] - c3[0][0], ay = c3[1][1] - c3[0][1], az = c3[1][2] - c3[0][2];
+  const double bx = c3[2][0] - c3[0][0], by = c3[2][1] - c3[0][1], bz = c3[2][2] - c3[0][2];
+  const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+  const double la = sqrt((ax * ax + ay * ay) + az * az);
+  const double e1x = ax / la, e1y = ay / la, e1z = az / la;
+  const double tx = ny * e1z - nz * e1y, ty = nz * e1x - nx * e1z, tz = nx * e1y - ny * e1x;
+  const double lt = sqrt((tx * tx + ty * ty) + tz * tz);
+  const double e2x = tx / lt, e2y = ty / lt, e2z = tz / lt;
+  v2 P[PTO_BAKE_MAXPTS];
+  int np = 3;
+  const int frame_ok = la > 0.0 && lt > 0.0 && finite_d(la) && finite_d(lt);
+  P[0].x = 0.0; P[0].y = 0.0;
+  P[1].x = (ax * e1x + ay * e1y) + az * e1z; P[1].y = (ax * e2x + ay * e2y) + az * e2z;
+  P[2].x = (bx * e1x + by * e1y) + bz * e1z; P[2].y = (bx * e2x + by * e2y) + bz * e2z;
+  for (int c = 0; c < 3; ++c) { F->pu[c] = cu[c]; F->pv[c] = cv[c]; F->pid[c] = PTO_NOIDX; }
+  const double A = frame_ok ? cross2(P[1].x - P[0].x, P[1].y - P[0].y, P[2].x - P[0].x, P[2].y - P[0].y) : 0.0;
+  if (frame_ok && A != 0.0 && finite_d(A)) {
+    F->frame_ok = 1;
+    for (int j = 0; j < nid; ++j) {                                   /* :505-537: project, barycentrics, keep what is inside */
+      const size_t id = ids[j];
+      const double dx = src_xyz[id] - c3[0][0], dy = src_xyz[n + id] - c3[0][1], dz = src_xyz[2 * n + id] - c3[0][2];
+      v2 X = {(dx * e1x + dy * e1y) + dz * e1z, (dx * e2x + dy * e2y) + dz * e2z};
+      double b[3];
+      bary2(X, P[0], P[1], P[2], A, b);
+      if (!(b[0] >= 0 && b[1] >= 0 && b[2] >= 0)) continue;
+      ++F->ninside;
+      int dup = 0;
+      for (int q = 0; q < np; ++q) dup |= (P[q].x == X.x && P[q].y == X.y);
+      if (dup) continue;
+      P[np] = X;
+      F->pu[np] = (b[0] * cu[0] + b[1] * cu[1]) + b[2] * cu[2];        /* :571-572 */
+      F->pv[np] = (b[0] * cv[0] + b[1] * cv[1]) + b[2] * cv[2];
+      F->pc[np][0] = src_rgb[3 * id]; F->pc[np][1] = src_rgb[3 * id + 1]; F->pc[np][2] = src_rgb[3 * id + 2];
+      F->pid[np] = (uint32_t)id;
+      ++np;
+    }
+  }
+  F->np = np;
+  for (int q = 0; q < np; ++q) { F->px[q] = P[q].x; F->py[q] = P[q].y; }
+  if (np == 3) return;                                                 /* :540-544: the face itself */
+  int64_t ntri = 0;                                                    /* at most 255 triangles per face (2 np - 5 <= 193 unless many points are co-circular) */
+  for (int i = 0; i < np - 2; ++i)                                     /* :546-581 with the build's Delaunay definition */
+    for (int j = i + 1; j < np - 1; ++j)
+      for (int kk = j + 1; kk < np; ++kk) {
+        const double o = cross2(P[j].x - P[i].x, P[j].y - P[i].y, P[kk].x - P[i].x, P[kk].y - P[i].y);
+        if (!(o != 0.0)) continue;
+        const int os = o > 0.0 ? 1 : -1;
+        int empty = 1;
+        for (int l = 0; l < np && empty; ++l) if (l != i && l != j && l != kk && in_circumcircle(P, i, j, kk, l, os)) empty = 0;
+        if (!empty) continue;
+        if (ntri < 255) { F->tri[ntri][0] = (uint8_t)i; F->tri[ntri][1] = (uint8_t)j; F->tri[ntri][2] = (uint8_t)kk; }
+        ++ntri;
+      }
+  F->ntri_all = ntri;
+  F->ntri = (int32_t)(ntri > 255 ? 255 : ntri);
+}
 int pto_bake_texture(const double* src_xyz, const uint8_t* src_rgb, uint64_t n, const double* vert_xyz, const double* vert_uv,
                      const uint8_t* vert_rgb, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
                      int R, uint8_t* bgra) {
   if (k < 1 || k > 32 || R < 1) return -1;
+  pto_bake_face* F = (pto_bake_face*)malloc(sizeof *F);
+  if (!F) return -1;
   for (uint64_t f = 0; f < nf; ++f) {
-    const int32_t* fv = faces + 3 * f;
-    if (fv[0] < 0 || fv[1] < 0 || fv[2] < 0 || (uint64_t)fv[0] >= nv || (uint64_t)fv[1] >= nv || (uint64_t)fv[2] >= nv) continue;   /* malformed face: skipped */
-    double cu[3], cv[3], c3[3][3];
-    uint8_t ccol[3][3];
-    for (int c = 0; c < 3; ++c) {
-      cu[c] = vert_uv[2 * (size_t)fv[c]]; cv[c] = vert_uv[2 * (size_t)fv[c] + 1];
-      for (int a = 0; a < 3; ++a) { c3[c][a] = vert_xyz[(size_t)a * nv + (size_t)fv[c]]; ccol[c][a] = vert_rgb[3 * (size_t)fv[c] + a]; }
-    }
-    /* union of the three corners' neighbour lists by original index, ascending (:470-479) */
-    uint32_t ids[96]; int nid = 0;
-    for (int c = 0; c < 3; ++c)
-      for (int j = 0; j < k; ++j) { const uint32_t id = nbr_idx[(size_t)fv[c] * k + j]; if (id != PTO_NOIDX && id < n) ids[nid++] = id; }
-    qsort(ids, (size_t)nid, sizeof(uint32_t), cmp_u32);
-    { int w = 0; for (int j = 0; j < nid; ++j) if (j == 0 || ids[j] != ids[j - 1]) ids[w++] = ids[j]; nid = w; }
-    /* plane frame (:485-494): origin corner 0, e1 along corner0 -> corner1, e2 = n x e1, both unit */
-    const double ax = c3[1][0] - c3[0][0], ay = c3[1][1] - c3[0][1], az = c3[1][2] - c3[0][2];
-    const double bx = c3[2][0] - c3[0][0], by = c3[2][1] - c3[0][1], bz = c3[2][2] - c3[0][2];
-    const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-    const double la = sqrt((ax * ax + ay * ay) + az * az);
-    const double e1x = ax / la, e1y = ay / la, e1z = az / la;
-    const double tx = ny * e1z - nz * e1y, ty = nz * e1x - nx * e1z, tz = nx * e1y - ny * e1x;
-    const double lt = sqrt((tx * tx + ty * ty) + tz * tz);
-    const double e2x = tx / lt, e2y = ty / lt, e2z = tz / lt;
-    v2 P[PTO_BAKE_MAXPTS];
-    double PU[PTO_BAKE_MAXPTS], PV[PTO_BAKE_MAXPTS];
-    uint8_t PC[PTO_BAKE_MAXPTS][3];
-    int np = 3;
-    const int frame_ok = la > 0.0 && lt > 0.0 && finite_d(la) && finite_d(lt);
-    P[0].x = 0.0; P[0].y = 0.0;
-    P[1].x = (ax * e1x + ay * e1y) + az * e1z; P[1].y = (ax * e2x + ay * e2y) + az * e2z;
-    P[2].x = (bx * e1x + by * e1y) + bz * e1z; P[2].y = (bx * e2x + by * e2y) + bz * e2z;
-    for (int c = 0; c < 3; ++c) { PU[c] = cu[c]; PV[c] = cv[c]; memcpy(PC[c], ccol[c], 3); }
-    const double A = frame_ok ? cross2(P[1].x - P[0].x, P[1].y - P[0].y, P[2].x - P[0].x, P[2].y - P[0].y) : 0.0;
-    if (frame_ok && A != 0.0 && finite_d(A)) {
-      for (int j = 0; j < nid; ++j) {                                   /* :505-537: project, barycentrics, keep what is inside */
-        const size_t id = ids[j];
-        const double dx = src_xyz[id] - c3[0][0], dy = src_xyz[n + id] - c3[0][1], dz = src_xyz[2 * n + id] - c3[0][2];
-        v2 X = {(dx * e1x + dy * e1y) + dz * e1z, (dx * e2x + dy * e2y) + dz * e2z};
-        double b[3];
-        bary2(X, P[0], P[1], P[2], A, b);
-        if (!(b[0] >= 0 && b[1] >= 0 && b[2] >= 0)) continue;
-        int dup = 0;
-        for (int q = 0; q < np; ++q) dup |= (P[q].x == X.x && P[q].y == X.y);
-        if (dup) continue;
-        P[np] = X;
-        PU[np] = (b[0] * cu[0] + b[1] * cu[1]) + b[2] * cu[2];          /* :571-572 */
-        PV[np] = (b[0] * cv[0] + b[1] * cv[1]) + b[2] * cv[2];
-        PC[np][0] = src_rgb[3 * id]; PC[np][1] = src_rgb[3 * id + 1]; PC[np][2] = src_rgb[3 * id + 2];
-        ++np;
-      }
-    }
-    if (np == 3) {                                                       /* :540-544 */
-      pto_draw_triangle(PU, PV, (const uint8_t(*)[3])PC, R, bgra);
+    pto_bake_one_face(src_xyz, src_rgb, n, vert_xyz, vert_uv, vert_rgb, nv, faces + 3 * f, nbr_idx, k, F);
+    if (!F->valid) continue;
+    if (F->np == 3) {                                                    /* :540-544 */
+      pto_draw_triangle(F->pu, F->pv, (const uint8_t(*)[3])F->pc, R, bgra);
       continue;
     }
-    int ntri = 0;                                                        /* at most 255 triangles per face (2 np - 5 <= 193 unless many points are co-circular) */
-    for (int i = 0; i < np - 2; ++i)                                     /* :546-581 with the build's Delaunay definition */
-      for (int j = i + 1; j < np - 1; ++j)
-        for (int kk = j + 1; kk < np; ++kk) {
-          const double o = cross2(P[j].x - P[i].x, P[j].y - P[i].y, P[kk].x - P[i].x, P[kk].y - P[i].y);
-          if (!(o != 0.0)) continue;
-          const int os = o > 0.0 ? 1 : -1;
-          int empty = 1;
-          for (int l = 0; l < np && empty; ++l) if (l != i && l != j && l != kk && in_circumcircle(P, i, j, kk, l, os)) empty = 0;
-          if (!empty || ntri >= 255) continue;
-          ++ntri;
-          const double tu[3] = {PU[i], PU[j], PU[kk]}, tv[3] = {PV[i], PV[j], PV[kk]};
-          uint8_t tc[3][3];
-          memcpy(tc[0], PC[i], 3); memcpy(tc[1], PC[j], 3); memcpy(tc[2], PC[kk], 3);
-          pto_draw_triangle(tu, tv, (const uint8_t(*)[3])tc, R, bgra);
-        }
+    for (int t = 0; t < F->ntri; ++t) {
+      const int i = F->tri[t][0], j = F->tri[t][1], kk = F->tri[t][2];
+      const double tu[3] = {F->pu[i], F->pu[j], F->pu[kk]}, tv[3] = {F->pv[i], F->pv[j], F->pv[kk]};
+      uint8_t tc[3][3];
+      memcpy(tc[0], F->pc[i], 3); memcpy(tc[1], F->pc[j], 3); memcpy(tc[2], F->pc[kk], 3);
+      pto_draw_triangle(tu, tv, (const uint8_t(*)[3])tc, R, bgra);
+    }
   }
+  free(F);
   return 0;
+}
+/* the report of face f alone (sizeof(pto_bake_face) bytes at `out`; oracle.py mirrors the layout) */
+int pto_bake_face_report(const double* src_xyz, const uint8_t* src_rgb, uint64_t n, const double* vert_xyz, const double* vert_uv,
+                         const uint8_t* vert_rgb, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
+                         uint64_t f, void* out) {
+  if (k < 1 || k > 32 || f >= nf) return -1;
+  pto_bake_one_face(src_xyz, src_rgb, n, vert_xyz, vert_uv, vert_rgb, nv, faces + 3 * f, nbr_idx, k, (pto_bake_face*)out);
+  return (int)sizeof(pto_bake_face);
 }
 /* reference :593-611: dilate(texture, 25x25 rect), edges = dilated & ~alpha (all four channels), padded = texture + edges
  * (saturating).  OpenCV's dilate ignores what lies outside the image (border value = the channel minimum). */

@@ -1,11 +1,25 @@
 """CPU checks of the texture-bake oracle (oracle/pt_oracle.c: pto_bake_texture, pto_dilate_pad) -- the build's definition of
 the reference's per-face bake (src/pointsTransfer.cpp:462-581, :66-107) and edge padding (:593-611) -- against independent
-restatements: a numpy rasteriser for the no-neighbour case, scipy's Delaunay for the number and total area of sub-triangles
-(through coverage), scipy.ndimage for the dilation."""
+restatements: a numpy rasteriser for the no-neighbour case, scipy.ndimage for the dilation, and, on the rows of
+_bake_cases.make_face_cases(), tests/_bake_ref.py -- DESIGN.md section 8 restated in numpy:
+  * rows in general position (every in-circle determinant verified non-zero and of the fp64 sign in exact arithmetic, no face left
+    out): the oracle's triangle SET equals scipy.spatial.Delaunay's, the areas add up to the face's, the count is 2 np - 2 - hull;
+  * lattice rows (co-circular, collinear, coincident points): the oracle's triangle LIST equals exhaustive empty-circle with exact
+    integer predicates, entry for entry, including which triples the 255 cap drops;
+  * every row: the whole atlas of _bake_ref.bake equals the oracle's byte for byte, and the row's reach holds on the face report;
+  * a triangle far outside the int range in UV returns at once (child process under a time limit)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
-from _bake_cases import make_case
+import _bake_ref as B
+from _bake_cases import ROW_NAMES, cloud_as, face_reports, make_case, make_face_cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROWS = {r["name"]: r for r in make_face_cases()}
 
 
 def _numpy_draw(tex, U, V, col, R):
@@ -85,3 +99,71 @@ def test_dilate_pad_against_scipy(oracle):
         mask = (~tex[:, :, 3])[:, :, None]
         want = np.minimum(tex.astype(np.int32) + (dil & mask).astype(np.int32), 255).astype(np.uint8)
         assert np.array_equal(got, want), ks
+
+
+# ---- the rows of _bake_cases.make_face_cases(): reach, triangulation against scipy / exact predicates, whole atlas against _bake_ref ----
+def test_vector_rasteriser_equals_the_scalar_one():
+    """_bake_ref.draw is _numpy_draw over the bounding box at once: same bytes, triangles partly and wholly outside included"""
+    rng = np.random.default_rng(70)
+    for R in (1, 7, 40):
+        a = np.zeros((R, R, 4), np.uint8); b = np.zeros((R, R, 4), np.uint8)
+        for _ in range(12):
+            U = rng.random(3) * 1.6 - 0.3; V = rng.random(3) * 1.6 - 0.3
+            col = rng.integers(0, 256, size=(3, 3))
+            _numpy_draw(a, U, V, col, R); B.draw(b, U, V, col, R)
+        assert np.array_equal(a, b) and (R < 40 or (a[:, :, 3] == 255).any())
+
+
+def _oracle_atlas(oracle, row, src, R):
+    return oracle.bake_texture(src, row["rgb"], row["verts"], row["uv"], np.clip(row["vrgb"], 0, 255).astype(np.uint8), row["faces"], row["lists"], R)
+
+
+@pytest.mark.parametrize("name", ROW_NAMES)
+def test_face_row_reach_triangulation_and_atlas(oracle, name):
+    row = ROWS[name]
+    skipped = 0
+    for ctype in row["types"]:
+        src = cloud_as(row, ctype)
+        reps = face_reports(oracle, row, ctype)
+        row["reach"](reps)
+        for f, r in enumerate(reps):
+            if not r["valid"] or r["np"] == 3:
+                assert r["ntri_all"] == 0
+                continue
+            P, T = r["xy"], r["tris"]
+            if row["tri"] == "scipy":
+                if not B.general_position(P):
+                    skipped += 1
+                    continue
+                want = B.scipy_delaunay(P)
+                assert r["ntri_all"] == len(T) == 2 * r["np"] - 2 - B.hull_size(P), (name, ctype, f)
+                assert set(map(tuple, T)) == set(map(tuple, want)), (name, ctype, f)
+                face2 = abs((P[1, 0] - P[0, 0]) * (P[2, 1] - P[0, 1]) - (P[1, 1] - P[0, 1]) * (P[2, 0] - P[0, 0]))
+                assert abs(B.tri_area2(P, T) - face2) <= 1e-12 * face2, (name, ctype, f)
+                assert np.array_equal(T, want)                       # and the oracle's order is the lexicographic one
+            else:
+                want = B.exact_delaunay(P)
+                assert r["ntri_all"] == len(want), (name, ctype, f, r["ntri_all"], len(want))
+                assert np.array_equal(T, want[:B.MAXTRI]), (name, ctype, f)
+        tri = B.scipy_delaunay if row["tri"] == "scipy" else B.exact_delaunay
+        for R in row["R"]:
+            got = _oracle_atlas(oracle, row, src, R)
+            want = B.bake(src, row["rgb"], row["verts"], row["uv"], row["vrgb"], row["faces"], row["lists"], R, tri)
+            assert np.array_equal(got, want), "%s %s R=%d: %d pixels differ" % (name, ctype, R, (got != want).any(axis=2).sum())
+    assert skipped == 0, "%s: %d faces are not in verified general position" % (name, skipped)
+
+
+def test_triangle_far_outside_the_int_range_returns():
+    """all three U R >= 2**31: the bounding box is rejected in double before any cast (it used to make the column loop run 2**31 times)"""
+    code = ("import numpy as np\nfrom oracle import oracle\n"
+            "verts = np.array([[0, 1, 0], [0, 0, 1], [0, 0, 0]], float)\n"
+            "none = np.full((3, 4), 0xFFFFFFFF, np.uint32)\n"
+            "for uv in ([[1e10, 0.1], [1e10 + 1, 0.2], [1e10, 0.9]], [[0.1, -1e10], [0.2, -1e10 - 1], [0.9, -1e10]], [[4e7, 4e7], [4e7 + 1, 4e7], [4e7, 4e7 + 1]]):\n"
+            "    tex = oracle.bake_texture(np.zeros((3, 4)), np.zeros((4, 3), np.uint8), verts, np.array(uv), np.full((3, 3), 200, np.uint8), np.array([[0, 1, 2]], np.int32), none, 64)\n"
+            "    assert not tex.any()\n"
+            "print('returned')\n")
+    try:
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=60)
+    except subprocess.TimeoutExpired:
+        pytest.fail("pto_draw_triangle did not return within 60 s on a triangle beyond the int range")
+    assert r.returncode == 0 and "returned" in r.stdout, r.stderr

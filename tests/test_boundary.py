@@ -367,6 +367,20 @@ def test_bench_refuses_more_ranks_than_devices():
     assert r.returncode != 0 and "visible GPUs" in r.stderr and not r.stdout.strip()
 
 
+def test_every_bake_row_runs_in_both_suites():
+    """each row of _bake_cases.ROW_NAMES is a collected case of the CPU module AND of the GPU module: a row cannot drop out of one suite"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _bake_cases import ROW_NAMES, make_face_cases
+    assert tuple(r["name"] for r in make_face_cases()) == ROW_NAMES and len(set(ROW_NAMES)) == len(ROW_NAMES) >= 26
+    r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "tests/test_bake_oracle.py", "tests/test_gpu_bake_paths.py"],
+                       cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    for mod, test in (("test_bake_oracle.py", "test_face_row_reach_triangulation_and_atlas"), ("test_gpu_bake_paths.py", "test_row_matches_oracle")):
+        for name in ROW_NAMES:
+            assert "%s::%s[%s]" % (mod, test, name) in r.stdout, (mod, name)
+
+
 def test_python_sources_are_import_clean():
     """Every Python file compiles and uses no undefined names (a NameError in a test that only ever SKIPS is found here, not on the
     first multi-GPU box): py_compile + a symbol-table pass over module- and function-level names."""
