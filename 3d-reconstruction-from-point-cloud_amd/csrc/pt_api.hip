@@ -763,13 +763,13 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
     // regions (10^3 cells) that fit the small capacity with headroom run the two-workgroups-per-CU geometry
     const bool empty_grid = c->adaptive && (c->st.n_refine > 0 || c->st.rho_occupied > 1.25 * c->rho / (1.0 - std::exp(-c->rho)));      // surfaces, clusters: most cells are empty
     const bool fits_small = (double)c->n / cells * 1000.0 * 1.05 <= (double)(k <= 8 ? PT_TILE_CAP_SMALL_8 : PT_TILE_CAP_SMALL_16);
-    // geometry: 1 = two 512-thread workgroups per CU (k <= 16), 4 = two 384-thread ones (k in 17..24), 0 = one large one.  A cloud that leaves most
-    // of its grid empty tries the two-per-CU geometry first whatever the average density says: its blocks that are over budget get the large one
-    const int tile_small = k <= 16 ? (c->tile == 2 || (c->tile == 1 && (fits_small || empty_grid)) ? 1 : 0)
-                                   : (k <= 24 ? (c->tile == 2 || (c->tile == 1 && (fits_small || empty_grid)) ? 4 : 0) : 0);
+    // A cloud that leaves most of its grid empty tries the two-per-CU geometry of its k (pt_tile_route.h) first whatever the average density
+    // says: its blocks that are over budget get the large one
+    const bool two_per_cu = k <= 24 && (c->tile == 2 || (c->tile == 1 && (fits_small || empty_grid)));
+    const TileGeometry geometry = !two_per_cu ? TileGeometry::Large : (k <= 16 ? TileGeometry::Small : TileGeometry::Medium);
     HIPCHK(c, hipMemsetAsync(todo_n, 0, 4, c->stream));
     const Attr* battr = br ? (const Attr*)c->attr.p : nullptr;
-    const bool second_chance = tile_small != 0;               // two-per-CU geometries: over-budget blocks get the large one
+    const bool second_chance = two_per_cu;                    // two-per-CU geometries: over-budget blocks get the large one
     // clouds that leave most of their grid empty (surfaces, clusters: the occupied cells hold far more than rho points, or the cell size
     // was refined): one workgroup per block that HOLDS TARGETS instead of one per block of the grid -- one read-back for the list's length
     const uint32_t* blist = nullptr;
@@ -788,14 +788,25 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       HIPCHK(c, hipMemsetAsync(retry_n, 0, 4, c->stream));
       RES(c, c->retry, (size_t)c->gp.nblocks * sizeof(uint32_t));
     }
-    c->st.tile_variant[0] = pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
-                       tile_small, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr, blist, nlist,
-                       second_chance ? (uint32_t*)c->retry.p : nullptr, retry_n, src64, tgt64, c->e_src, c->stream, bound2_dev, c->cap2);
+    TileLaunch tl{};
+    tl.gp = c->gp; tl.src = src32; tl.cell_start = (const uint32_t*)c->cell_start.p; tl.tgt = tgt32; tl.tblock_start = c->ttb.block_start; tl.k = k;
+    tl.out_idx = idx_dev; tl.out_d2 = d2_dev;
+    tl.todo = (uint32_t*)c->todo.p; tl.todo_n = todo_n;
+    tl.geometry = geometry;
+    tl.blend = TileBlend{battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr};
+    tl.blocks = blist; tl.nblocks_listed = nlist;
+    tl.retry = second_chance ? (uint32_t*)c->retry.p : nullptr; tl.retry_n = retry_n;
+    tl.dbl = TileDouble{src64, tgt64, c->e_src};
+    tl.bound = bound2_dev; tl.cap2 = c->cap2;
+    tl.stream = c->stream;
+    c->st.tile_variant[0] = pt_launch_knn_tile(tl);
     if (second_chance) {
       retry_launch = [=]() {
-        c->st.tile_variant[1] = pt_launch_knn_tile(c->gp, src32, (const uint32_t*)c->cell_start.p, tgt32, c->ttb.block_start, k, idx_dev, d2_dev, (uint32_t*)c->todo.p, todo_n,
-                           0, battr, (uint32_t)c->n_total, br ? br->mode : 0, br ? br->rgb_out : nullptr, br ? br->nrm_out : nullptr,
-                           (const uint32_t*)c->retry.p, c->h_counter[RB_RETRY], nullptr, nullptr, src64, tgt64, c->e_src, c->stream, bound2_dev, c->cap2);
+        TileLaunch r = tl;                      // the same launch in the large geometry, over the blocks the first one listed
+        r.geometry = TileGeometry::Large;
+        r.blocks = (const uint32_t*)c->retry.p; r.nblocks_listed = c->h_counter[RB_RETRY];
+        r.retry = nullptr; r.retry_n = nullptr;
+        c->st.tile_variant[1] = pt_launch_knn_tile(r);
       };
       HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_RETRY, retry_n, 4, hipMemcpyDeviceToHost, c->stream));
       // (round 4) when the leftover pass reads the todo list's length anyway -- one wave per leftover target -- the two counts share that

@@ -1,8 +1,9 @@
 // pt_internal.h -- host-side launch interface between the C-ABI glue (pt_api.hip) and the kernel
-// translation units (pt_grid.hip, pt_query.hip, pt_attr.hip).  Everything takes the stream to launch on;
+// translation units (pt_grid.hip, pt_knn_group.hip / pt_knn_wave.hip / pt_knn_tile.hip, pt_query.hip, pt_attr.hip, ...).  Everything takes the stream to launch on;
 // nothing here allocates or synchronises.
 #pragma once
 #include "pt_common.h"
+#include "pt_tile_route.h"
 
 // tables used by one sort (source cloud or target set)
 struct SortTables {
@@ -83,7 +84,7 @@ uint32_t pt_sort_num_chunks(uint32_t n, size_t rec_size);
 // generic exclusive scan of u32 (n <= 2048*2048*... see pt_grid.hip); out may alias in
 void pt_launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tmp, hipStream_t s);
 
-// ---- pt_query.hip -----------------------------------------------------------------------------
+// ---- pt_knn_group.hip, pt_knn_tile.hip, pt_query.hip ------------------------------------------------
 // k-NN of m sorted target records against the sorted source records.  bound2 (may be null) is indexed by
 // the target's id.  Results go to out_idx/out_d2 at row `id` (k entries per row).
 template <class Rec>
@@ -98,23 +99,42 @@ uint32_t pt_mark_tiles(uint32_t m);
 // the marks without the group kernel: every listed target (list == null: all m) gets 1, or 2 when its own cell carries the `near` flag
 template <class Rec>
 void pt_launch_mark_near(const GridParams& gp, const Rec* tgt, const uint32_t* list, const uint32_t* list_n, uint32_t m, const uint8_t* near, uint8_t* mark, hipStream_t s);
-// quad-per-target LDS tile kernel (fp32 records, k <= 32); leftovers go to todo[*todo_n] and are finished by pt_launch_knn(list=todo)
-// staged-region capacities (records) of the tile kernel's geometries: what is left of 80 KB (two workgroups per CU) or
-// 160 KB (one) after the per-lane queue segments and the cell table
 // the blocks with at least one target (tblock_start: the target sort's block table), appended to list[*count] (count zeroed here)
 void pt_launch_tblock_list(const uint32_t* tblock_start, uint32_t nblocks, uint32_t* list, uint32_t* count, hipStream_t s);
-constexpr int PT_TILE_CAP_SMALL_8 = 4400, PT_TILE_CAP_SMALL_16 = 3888, PT_TILE_CAP_LARGE = 8448, PT_TILE_CAP_WIDE = 8960;
 constexpr int PT_TILE_MAX_K = 32;      // beyond this the group kernel answers everything
-// the route code of one tile launch (pt_stats_t::tile_variant, include/pt_api.h): the instantiation's template arguments, packed
-#define PT_TILE_CODE(K, TWG, WIDE, BLEND, DBL, KC, BND, LISTED)                                                                          \
-  ((uint32_t)(K) | (uint32_t)(KC) << 6 | (uint32_t)((TWG) / 64) << 12 | (uint32_t)(bool)(WIDE) << 16 | (uint32_t)(bool)(BLEND) << 17 | \
-   (uint32_t)(bool)(DBL) << 18 | (uint32_t)(bool)(BND) << 19 | (uint32_t)(bool)(LISTED) << 20)
-// returns the launch's PT_TILE_CODE (0: no launch)
-uint32_t pt_launch_knn_tile(const GridParams& gp, const RecF* src, const uint32_t* cell_start, const RecF* tgt, const uint32_t* tblock_start,
-                            int k, uint32_t* out_idx, double* out_d2, uint32_t* todo, uint32_t* todo_n, int geometry, const Attr* attr, uint32_t n_attr,
-                            int mode, float* rgb_out, float* nrm_out, const uint32_t* blocks, uint32_t nblocks_listed, uint32_t* retry,
-                            uint32_t* retry_n, const RecD* src_exact, const RecD* tgt_exact, float e_src, hipStream_t s, const double* bound = nullptr,
-                            double cap2 = INFINITY);   // bound (per target) and / or cap2 < +inf (max_dist squared): the bounded variants; with attr they blend too
+// attribute blend fused into the tile kernel (attr == null: none): the table, its length, the mode and the two outputs
+struct TileBlend { const Attr* attr; uint32_t n_attr; int mode; float* rgb_out; float* nrm_out; };
+// fp64 clouds (src != null): the LDS image and the two fp32 passes work on fp32-ROUNDED coordinates (the build's shadow records,
+// whose id field is the sorted position), under a bound widened by the rounding; pass 3 fetches the exact 32-byte
+// records of the queued candidates by position.  src / tgt: the exact records; e_src: largest |coordinate| rounding
+// error of a source point (2^-24 * largest |coordinate| of the cloud's bounding box).
+struct TileDouble { const RecD* src; const RecD* tgt; float e_src; };
+// One launch of the quad-per-target LDS tile kernel (fp32 records, k <= 32) over all blocks, or over a list of them.  Targets it cannot
+// settle are appended to todo[*todo_n] (todo_n zeroed by the caller) and finished by pt_launch_knn(list = todo).
+struct TileLaunch {
+  GridParams gp;
+  const RecF* src;                 // sorted source records (fp64 clouds: their fp32 shadow)
+  const uint32_t* cell_start;
+  const RecF* tgt;                 // block-sorted targets (fp64 clouds: unused, dbl.tgt has them)
+  const uint32_t* tblock_start;
+  int k;
+  uint32_t* out_idx;
+  double* out_d2;
+  uint32_t* todo;
+  uint32_t* todo_n;
+  TileGeometry geometry;           // what the caller asks for; pt_tile_route (pt_tile_route.h) decides what runs
+  TileBlend blend;                 // the neighbours' attributes are blended in the same pass (rows of the settled targets only)
+  const uint32_t* blocks;          // run over these nblocks_listed blocks instead of every block of the grid (null: all)
+  uint32_t nblocks_listed;
+  uint32_t* retry;                 // blocks over this geometry's region budget but within the large one's are listed here (count in
+  uint32_t* retry_n;               //   *retry_n) instead of going to `todo`, for a second launch over that list (null: none)
+  TileDouble dbl;
+  const double* bound;             // per-target bounds by target id (may be null) and / or cap2 < +inf (max_dist squared): the bounded
+  double cap2;                     //   variants; with blend.attr they blend too
+  hipStream_t stream;
+};
+// returns the launch's route code (pt_tile_code, pt_tile_route.h; 0: no launch)
+uint32_t pt_launch_knn_tile(const TileLaunch& t);
 template <class T>
 void pt_launch_request_pack(const T* x, const T* y, const T* z, const double* d2, uint32_t m, int k, int axis, const double* bounds_dev, int g,
                             int my_slab, double cap2, uint32_t* count, uint32_t* sel, double* pkt, hipStream_t s);

@@ -10,7 +10,7 @@
 //   * membership: sub = clamp(floor((u - node origin) * cells-per-unit), 0, 7) per axis with u = (p - bbmin) / h, the position
 //     in level-0 cell units; origins and scales are dyadic rationals, exact in fp64, and the query computes the very same
 //     expression, so build and search agree on every point.
-// The search over this structure (HierScan, used by the group kernel knn_kernel<.., HIER = true>) is in pt_query.hip.
+// The search over this structure (HierScan, used by the group kernel knn_kernel<.., HIER = true>) is in pt_knn_group.hip.
 #include "pt_internal.h"
 
 namespace {

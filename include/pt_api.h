@@ -113,7 +113,7 @@ typedef struct pt_stats_t {
   /* The route of the last query (of pt_stream_query: its last searched chunk; of the exchange: its last search), reset by every query
    * and valid whether "sync" is set or not -- none of them needs a read-back the query does not make anyway. */
   uint32_t tile_variant[2]; /* the LDS tile kernel's instantiation: [0] its first launch, [1] the large-geometry retry launch over the blocks the
-                             * two-per-CU geometry passed on; 0 = no such launch.  Bits (PT_TILE_CODE in csrc/pt_internal.h): 0-5 K (the list
+                             * two-per-CU geometry passed on; 0 = no such launch.  Bits (pt_tile_code in csrc/pt_tile_route.h): 0-5 K (the list
                              * width: 8, 16, 32), 6-11 KC (the pass-1 chain), 12-15 threads per workgroup / 64, 16 WIDE queue, 17 BLEND (fused
                              * blend), 18 DBL (fp64 cloud: fp32 shadow, exact records in pass 3), 19 BND (per-target bounds and / or the cap),
                              * 20 the launch ran over a list of blocks (tile_sparse, or the retry) */

@@ -1,6 +1,7 @@
 """Every compiled instantiation of the LDS tile kernel and how a query reaches it (shared by the CPU and GPU suites).
 
-csrc/pt_query.hip, pt_launch_knn_tile, launches knn_tile_kernel<K, CAP, TWG, WIDE, BLEND, DBL, KC, BND>.  Which one runs depends on
+csrc/pt_knn_tile.hip, pt_launch_knn_tile, launches knn_tile_kernel<K, CAP, TWG, WIDE, BLEND, DBL, KC, BND>; csrc/pt_tile_route.h decides
+K, CAP, TWG, WIDE and KC (expected_route below says the same in Python).  Which one runs depends on
   - k: K (the list width) and KC (the pass-1 chain) of the k bucket;
   - the geometry: small (512 threads, k <= 16), medium (384 threads, k in 17..24), large (768 threads), wide (512 threads, k in 25..32,
     whatever the geometry).  pt_set_param("tile", 2) asks for small / medium, ("tile", 3) for large;
@@ -12,7 +13,7 @@ A small or medium launch hands the blocks over its budget to a second launch of 
 over a list of those blocks (the retry).  The table below has one row per instantiation; test_boundary checks it against the
 instantiations the compiler emitted, test_gpu_tile_variants runs every row and checks that the row's instantiation answered."""
 
-CAP_SMALL_8, CAP_SMALL_16, CAP_LARGE, CAP_WIDE = 4400, 3888, 8448, 8960           # PT_TILE_CAP_* (csrc/pt_internal.h)
+CAP_SMALL_8, CAP_SMALL_16, CAP_LARGE, CAP_WIDE = 4400, 3888, 8448, 8960           # PT_TILE_CAP_* (csrc/pt_tile_route.h)
 
 # The launcher's geometry cells: (geometry, K, CAP, TWG, WIDE, KC, k values to run: first, middle, last of the bucket)
 _SMALL = [("small", 8, CAP_SMALL_8, 512, False, 8, (1, 5, 8)), ("small", 16, CAP_SMALL_16, 512, False, 16, (9, 13, 16))]
@@ -49,13 +50,28 @@ def _rows():
 ROWS = _rows()
 
 
+def expected_route(k, geometry, bound):
+    """(K, CAP, TWG, WIDE, KC) of the launch that answers k neighbours when the caller asks for `geometry` ("large", "small", "medium")
+    with bound "none", "stream" (per-target bounds without a cap) or "cap", read off ROWS: k in 25..32 runs the wide row whatever is
+    asked for; the geometry asked for runs if it has a row for k; everything else runs the large one.  One exception: the BOUNDED
+    medium geometry is launched only under a cap -- uncapped streamed chunks keep the large geometry they always had."""
+    kc = min(r["KC"] for r in ROWS if k <= r["KC"])           # the k buckets end at the KC values: 8, 16, 20, 24, 32
+    if geometry == "medium" and bound == "stream":
+        geometry = "large"
+    for geo in ("wide", geometry, "large"):
+        for r in ROWS:
+            if r["geometry"] == geo and r["KC"] == kc:
+                return (r["K"], r["CAP"], r["TWG"], r["WIDE"], r["KC"])
+    raise ValueError("no row for k = %d" % k)
+
+
 def instantiation(row):
     """(K, CAP, TWG, WIDE, BLEND, DBL, KC, BND) -- the template arguments, in knn_tile_kernel's order"""
     return (row["K"], row["CAP"], row["TWG"], row["WIDE"], row["BLEND"], row["DBL"], row["KC"], row["BND"])
 
 
 def code(K, TWG, WIDE, BLEND, DBL, KC, BND, listed=False):
-    """pt_stats_t::tile_variant of a launch (PT_TILE_CODE, csrc/pt_internal.h)"""
+    """pt_stats_t::tile_variant of a launch (pt_tile_code, csrc/pt_tile_route.h)"""
     return K | KC << 6 | (TWG // 64) << 12 | int(WIDE) << 16 | int(BLEND) << 17 | int(DBL) << 18 | int(BND) << 19 | int(listed) << 20
 
 

@@ -124,10 +124,12 @@ _ASM = []
 
 
 def _query_asm():
-    """the device assembly of csrc/pt_query.hip (`make asm`), built once per session"""
+    """the device assembly of the three search-kernel files, csrc/pt_knn_tile.hip, pt_knn_group.hip and pt_knn_wave.hip (`make asm`),
+    concatenated; built once per session"""
     if not _ASM:
         subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "-s", "asm"])
-        _ASM.append(open(os.path.join(PKG, "csrc", "_build", "asm", "pt_query-hip-amdgcn-amd-amdhsa-gfx950.s")).read())
+        _ASM.append("".join(open(os.path.join(PKG, "csrc", "_build", "asm", "%s-hip-amdgcn-amd-amdhsa-gfx950.s" % f)).read()
+                            for f in ("pt_knn_tile", "pt_knn_group", "pt_knn_wave")))
     return _ASM[0]
 
 
@@ -198,6 +200,28 @@ def test_tile_variant_table_equals_the_compiled_instantiations():
         d = TV.decode(TV.row_code(r))
         assert (d["K"], d["TWG"], d["WIDE"], d["BLEND"], d["DBL"], d["KC"], d["BND"], d["listed"]) == \
             (r["K"], r["TWG"], r["WIDE"], r["BLEND"], r["DBL"], r["KC"], r["BND"], False)
+
+
+def test_tile_route_table_is_the_one_the_variant_table_describes(tmp_path):
+    """csrc/pt_tile_route.h -- the one place the tile launcher's k bucket x geometry decision is written -- against
+    tests/_tile_variants.py: host/tile_route_selftest.cpp prints the route of every k in 1..32 x {large, small, medium} x {unbounded,
+    per-target bounds without a cap, cap}, and every line equals _tile_variants.expected_route (which reads ROWS)."""
+    import _tile_variants as TV
+    exe = str(tmp_path / "tile_route_selftest")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", exe, os.path.join(PKG, "host", "tile_route_selftest.cpp")])
+    lines = subprocess.check_output([exe], text=True).splitlines()
+    assert len(lines) == 32 * 3 * 3
+    seen = set()
+    for line in lines:
+        k, geo, bound, K, cap, twg, wide, kc = line.split()
+        seen.add((int(k), geo, bound))
+        assert (int(K), int(cap), int(twg), wide == "1", int(kc)) == TV.expected_route(int(k), geo, bound), line
+    assert seen == {(k, g, b) for k in range(1, 33) for g in ("large", "small", "medium") for b in ("none", "stream", "cap")}
+    # ... and every row of the table is what its own query gets: the row's k values, asked for in the row's geometry under its bound
+    for r in TV.ROWS:
+        for k in r["ks"]:
+            geo = "large" if r["geometry"] == "wide" else r["geometry"]
+            assert TV.expected_route(k, geo, r["bound"]) == (r["K"], r["CAP"], r["TWG"], r["WIDE"], r["KC"]), (r["id"], k)
 
 
 def _c_struct_members(txt, name):

@@ -1,4 +1,4 @@
-"""Kernel resource usage of one .hip file (dev helper): python tools/kres.py pt_query.hip [filter]"""
+"""Kernel resource usage of one .hip file (dev helper): python tools/kres.py pt_knn_tile.hip [filter]"""
 import re, subprocess, sys, os
 src = sys.argv[1]; flt = sys.argv[2] if len(sys.argv) > 2 else ""
 d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "3d-reconstruction-from-point-cloud_amd", "csrc")

@@ -9,8 +9,8 @@ if [ "$1" != run ]; then
   make -C $csrc -j8 >/dev/null; mkdir -p $csrc/_build/ab tools/_ab; rm -f tools/_ab/libpt_sw_*.so
   for spec in "$@"; do
     name=${spec%%:*}; flags=${spec#*:}
-    ( cd $csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math $flags -c pt_query.hip -o _build/ab/pt_query_sw_$name.o &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/_ab/libpt_sw_$name.so _build/ab/pt_query_sw_$name.o _build/pt_grid.o _build/pt_attr.o _build/pt_bake.o _build/pt_exchange.o _build/pt_refine.o _build/pt_api.o ) &
+    ( cd $csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math $flags -c pt_knn_wave.hip -o _build/ab/pt_knn_wave_sw_$name.o &&
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/_ab/libpt_sw_$name.so _build/ab/pt_knn_wave_sw_$name.o $(ls _build/*.o | grep -v pt_knn_wave.o) ) &
   done
   wait; exit 0
 fi
