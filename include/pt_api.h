@@ -280,7 +280,11 @@ int  pt_blend_dev(pt_ctx*, const uint32_t* idx_dev, const double* d2_dev_or_null
 int  pt_blend_weighted(pt_ctx*, const uint32_t* idx, const double* w, uint64_t m, int k, float* rgb_out, float* nrm_out);
 int  pt_blend_weighted_dev(pt_ctx*, const uint32_t* idx_dev, const double* w_dev, uint64_t m, int k,
                            float* rgb_out_dev, float* nrm_out_dev);
-/* PCA normal of the k neighbours (BASELINE config 3); needs the whole cloud resident (no slabs). */
+/* PCA normal of the k neighbours (BASELINE config 3); needs the whole cloud resident (no slabs: PT_ERR_UNSUPPORTED).  Unit eigenvector
+ * of the smallest eigenvalue of the covariance of the entries that name a point (idx != PT_NOIDX and idx < n), oriented so that its dot
+ * product with the sum of those points' stored normals is >= 0 (its z component >= 0 where no attribute table is resident).  A row with
+ * fewer than three such entries -- an empty row included -- gets (0, 0, 1).  That holds under a "max_dist" cap too: unlike the capped
+ * blends, PCA writes every row. */
 int  pt_pca_normals(pt_ctx*, const uint32_t* idx, uint64_t m, int k, float* nrm_out);
 int  pt_pca_normals_dev(pt_ctx*, const uint32_t* idx_dev, uint64_t m, int k, float* nrm_out_dev);
 

@@ -63,7 +63,7 @@ def lib():
         L.pto_kdtree_query.argtypes = [p, p, u64, i32, p, p, i32]
         L.pto_num_threads.restype = i32
         L.pto_merge_candidates.argtypes = [p, p, i32, u64, i32, p, p]
-        L.pto_blend.argtypes = [p, p, u64, i32, i32, p, p, p, p]
+        L.pto_blend.argtypes = [p, p, u64, i32, i32, p, p, u64, p, p]
         L.pto_blend_weighted.argtypes = [p, p, u64, i32, p, p, p, p]
         L.pto_pca_normals.argtypes = [p, u64, i32, p, u64, p, p, p]
         L.pto_bake_texture.argtypes = [p, p, u64, p, p, p, u64, p, u64, p, i32, i32, p]
@@ -206,12 +206,15 @@ def merge_candidates(idx_lists, d2_lists):
 
 # ---- blend / PCA (build-defined; see pt_oracle.c) ---------------------------
 def blend(idx, d2, rgb, nrm, mode=0):
+    """Entries that name no record (NOIDX, or an id beyond the attribute arrays) are skipped, as the kernels skip them."""
     idx = np.ascontiguousarray(idx, np.uint32); d2 = np.ascontiguousarray(d2, np.float64)
     m, k = idx.shape
     rgb = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
     nrm = None if nrm is None else np.ascontiguousarray(nrm, np.float32)
     ro = np.zeros((m, 3), np.float32); no = np.zeros((m, 3), np.float32)
-    rc = lib().pto_blend(_ptr(idx), _ptr(d2), m, k, mode, _ptr(rgb), _ptr(nrm), _ptr(ro), _ptr(no))
+    n = rgb.shape[0] if rgb is not None else (nrm.shape[0] if nrm is not None else 0)
+    assert rgb is None or nrm is None or nrm.shape[0] == n, "rgb and nrm describe the same n points"
+    rc = lib().pto_blend(_ptr(idx), _ptr(d2), m, k, mode, _ptr(rgb), _ptr(nrm), n, _ptr(ro), _ptr(no))
     assert rc == 0
     return ro, no
 

@@ -502,14 +502,16 @@ int pto_merge_candidates(const uint32_t* idx_lists, const double* d2_lists, int 
 /*   mode 1: w_j = (1/(d2_j + 1e-12)) / sum (inverse squared distance)         */
 /* colours: float 0..255 (not truncated); normals: blended then renormalised   */
 /* (left as is if length < 1e-12).  rgb: u8 [n][3]; nrm: f32 [n][3].           */
+/* An entry that names no record (PTO_NOIDX, or id >= n) is skipped, as the    */
+/* kernels skip it.                                                            */
 /* ------------------------------------------------------------------------- */
 int pto_blend(const uint32_t* idx, const double* d2, uint64_t m, int k, int mode,
-              const uint8_t* rgb, const float* nrm, float* rgb_out, float* nrm_out) {
+              const uint8_t* rgb, const float* nrm, uint64_t n, float* rgb_out, float* nrm_out) {
   for (uint64_t t = 0; t < m; ++t) {
     double w[64]; double wsum = 0.0; int ke = 0;
     if (k > 64) return -1;
     for (int j = 0; j < k; ++j) {
-      if (idx[t * k + j] == PTO_NOIDX) { w[j] = 0.0; continue; }
+      if (idx[t * k + j] == PTO_NOIDX || idx[t * k + j] >= n) { w[j] = 0.0; continue; }
       ++ke;
       w[j] = (mode == 1) ? 1.0 / (d2[t * k + j] + 1e-12) : 1.0;
       wsum += w[j];
@@ -517,7 +519,7 @@ int pto_blend(const uint32_t* idx, const double* d2, uint64_t m, int k, int mode
     double c[3] = {0, 0, 0}, nn[3] = {0, 0, 0};
     for (int j = 0; j < k; ++j) {
       const uint32_t id = idx[t * k + j];
-      if (id == PTO_NOIDX) continue;
+      if (id == PTO_NOIDX || id >= n) continue;
       const double wj = w[j] / wsum;
       for (int a = 0; a < 3; ++a) {
         if (rgb) c[a] += wj * (double)rgb[3 * (size_t)id + a];
@@ -571,7 +573,8 @@ int pto_blend_weighted(const uint32_t* idx, const double* w, uint64_t m, int k, 
 /* neighbours' 3x3 covariance (double, Jacobi), sign-oriented so that          */
 /* dot(n, mean of the neighbours' stored normals) >= 0 (or +z if nrm is NULL). */
 /* `planarity` (may be NULL) receives lambda_min / (lambda_0+lambda_1+lambda_2) */
-/* so tests can skip ill-conditioned neighbourhoods.                           */
+/* so tests can skip ill-conditioned neighbourhoods.  An entry that names no   */
+/* point (PTO_NOIDX, or id >= n) is skipped, as the kernels skip it.           */
 /* ------------------------------------------------------------------------- */
 static void jacobi3(double a[3][3], double v[3][3], double ev[3]) {
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) v[i][j] = (i == j);
@@ -596,7 +599,7 @@ int pto_pca_normals(const uint32_t* idx, uint64_t m, int k, const double* src, u
   for (uint64_t t = 0; t < m; ++t) {
     double mu[3] = {0, 0, 0}, mn[3] = {0, 0, 0}; int ke = 0;
     for (int j = 0; j < k; ++j) {
-      const uint32_t id = idx[t * k + j]; if (id == PTO_NOIDX) continue;
+      const uint32_t id = idx[t * k + j]; if (id == PTO_NOIDX || id >= n) continue;
       mu[0] += sx[id]; mu[1] += sy[id]; mu[2] += sz[id]; ++ke;
       if (nrm) for (int a = 0; a < 3; ++a) mn[a] += (double)nrm[3 * (size_t)id + a];
     }
@@ -604,7 +607,7 @@ int pto_pca_normals(const uint32_t* idx, uint64_t m, int k, const double* src, u
     for (int a = 0; a < 3; ++a) mu[a] /= ke;
     double cv[3][3] = {{0}};
     for (int j = 0; j < k; ++j) {
-      const uint32_t id = idx[t * k + j]; if (id == PTO_NOIDX) continue;
+      const uint32_t id = idx[t * k + j]; if (id == PTO_NOIDX || id >= n) continue;
       const double d[3] = {sx[id] - mu[0], sy[id] - mu[1], sz[id] - mu[2]};
       for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) cv[a][b] += d[a] * d[b];
     }
