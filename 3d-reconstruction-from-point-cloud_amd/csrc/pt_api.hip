@@ -2239,8 +2239,8 @@ int pt_exchange_merge_local(pt_ctx* const* ctxs, int g, const void* const* tgt_x
 }
 
 // ---- texture bake (pt_bake.hip) ------------------------------------------------------------------------------------
-int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
-                    int resolution, int pad_ksize, uint8_t* bgra_out) {
+int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
+                 int resolution, int pad_ksize, int maps, uint8_t* color_bgra_out, uint8_t* normal_bgra_out) {
   if (!c) return PT_ERR_ARG;
   if (c->src_type != PT_F32 && c->src_type != PT_F64) return fail(c, PT_ERR_STATE, "no source cloud resident (call a pt_build_* first)");
   if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "the texture bake needs the whole cloud resident (not a slab)");
@@ -2248,17 +2248,24 @@ int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [1, %d]", k, PT_MAX_K);
   if (resolution < 1 || resolution > 32768) return fail(c, PT_ERR_ARG, "resolution out of range [1, 32768]");
   if (pad_ksize < 0 || (pad_ksize > 0 && !(pad_ksize & 1)) || pad_ksize > 255) return fail(c, PT_ERR_ARG, "pad_ksize must be 0 or an odd number <= 255");
-  if (!bgra_out || (nv && !mesh_vertices) || (nf && (!faces || !nbr_idx))) return fail(c, PT_ERR_ARG, "null argument");
+  if (maps < 1 || (maps & ~(PT_MAP_COLOR | PT_MAP_NORMAL))) return fail(c, PT_ERR_ARG, "maps = %d: a non-empty subset of PT_MAP_COLOR | PT_MAP_NORMAL", maps);
+  const bool want_c = (maps & PT_MAP_COLOR) != 0, want_n = (maps & PT_MAP_NORMAL) != 0;
+  if ((want_c && !color_bgra_out) || (want_n && !normal_bgra_out) || (nv && !mesh_vertices) || (nf && (!faces || !nbr_idx))) return fail(c, PT_ERR_ARG, "null argument");
   if (nf >= (1ull << 24)) return fail(c, PT_ERR_ARG, "nf = %llu: the pixel key holds 24 bits of face index", (unsigned long long)nf);
   { int r = check_n(c, nv, "nv"); if (r) return r; }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t npix = (size_t)resolution * (size_t)resolution;
-  DevBuf keys, tex, tmp, out, dv, df, dn;
-  auto cleanup = [&]() { DevBuf* all[] = {&keys, &tex, &tmp, &out, &dv, &df, &dn}; for (DevBuf* b : all) release(c, *b); };
+  // keys: one plane per requested map, the colour plane first; per map the resolved image and (padding) the padded one; tmp is shared
+  DevBuf keys, tex[2], out[2], tmp, dv, df, dn;
+  const size_t nplanes = (want_c ? 1 : 0) + (want_n ? 1 : 0);
+  uint8_t* const host[2] = {color_bgra_out, normal_bgra_out};
+  const bool want[2] = {want_c, want_n};
+  auto cleanup = [&]() { DevBuf* all[] = {&keys, &tex[0], &tex[1], &out[0], &out[1], &tmp, &dv, &df, &dn}; for (DevBuf* b : all) release(c, *b); };
   auto run = [&]() -> int {
-    RES(c, keys, npix * 8); RES(c, tex, npix * 4);
+    RES(c, keys, nplanes * npix * 8);
+    for (int p = 0; p < 2; ++p) if (want[p]) RES(c, tex[p], npix * 4);
     RES(c, dv, std::max<uint64_t>(nv, 1) * sizeof(pt_point)); RES(c, df, std::max<uint64_t>(nf, 1) * 12); RES(c, dn, std::max<uint64_t>(nv, 1) * (size_t)k * 4);
-    HIPCHK(c, hipMemsetAsync(keys.p, 0, npix * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(keys.p, 0, nplanes * npix * 8, c->stream));
     { int r = copy_in(c, dv.p, mesh_vertices, nv * sizeof(pt_point), 0); if (r) return r; }
     { int r = copy_in(c, df.p, faces, nf * 12, 0); if (r) return r; }
     { int r = copy_in(c, dn.p, nbr_idx, nv * (size_t)k * 4, 0); if (r) return r; }
@@ -2267,22 +2274,27 @@ int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const
       const float* x = nullptr;
       { int r = source_xyz_f32(c, &x); if (r) return r; }
       pt_launch_bake_faces<float>(x, x + c->n, x + 2 * c->n, (const Attr*)c->attr.p, (uint32_t)c->n, dv.p, (uint32_t)nv, (const int32_t*)df.p, (uint32_t)nf,
-                                  (const uint32_t*)dn.p, k, resolution, (unsigned long long*)keys.p, c->stream);
+                                  (const uint32_t*)dn.p, k, resolution, maps, (unsigned long long*)keys.p, c->stream);
     } else {
       const double* x = (const double*)c->in_xyz.p;
       pt_launch_bake_faces<double>(x, x + c->n, x + 2 * c->n, (const Attr*)c->attr.p, (uint32_t)c->n, dv.p, (uint32_t)nv, (const int32_t*)df.p, (uint32_t)nf,
-                                   (const uint32_t*)dn.p, k, resolution, (unsigned long long*)keys.p, c->stream);
+                                   (const uint32_t*)dn.p, k, resolution, maps, (unsigned long long*)keys.p, c->stream);
     }
-    pt_launch_bake_resolve((const unsigned long long*)keys.p, (uint32_t*)tex.p, npix, c->stream);
-    const void* result = tex.p;
-    if (pad_ksize > 0) {
-      RES(c, tmp, npix * 4); RES(c, out, npix * 4);
-      pt_launch_dilate_pad((const uint32_t*)tex.p, (uint32_t*)tmp.p, (uint32_t*)out.p, resolution, pad_ksize, c->stream);
-      result = out.p;
+    const void* result[2] = {nullptr, nullptr};
+    for (int p = 0; p < 2; ++p) {
+      if (!want[p]) continue;
+      pt_launch_bake_resolve((const unsigned long long*)keys.p + (p && want_c ? npix : 0), (uint32_t*)tex[p].p, npix, c->stream);
+      result[p] = tex[p].p;
+      if (pad_ksize > 0) {
+        if (!tmp.p) RES(c, tmp, npix * 4);
+        RES(c, out[p], npix * 4);
+        pt_launch_dilate_pad((const uint32_t*)tex[p].p, (uint32_t*)tmp.p, (uint32_t*)out[p].p, resolution, pad_ksize, c->stream);
+        result[p] = out[p].p;
+      }
     }
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(bgra_out, result, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    for (int p = 0; p < 2; ++p) if (want[p]) HIPCHK(c, hipMemcpyAsync(host[p], result[p], npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
@@ -2292,6 +2304,11 @@ int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const
   const int r = run();
   cleanup();
   return r;
+}
+
+int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
+                    int resolution, int pad_ksize, uint8_t* bgra_out) {
+  return pt_bake_maps(c, mesh_vertices, nv, faces, nf, nbr_idx, k, resolution, pad_ksize, PT_MAP_COLOR, bgra_out, nullptr);
 }
 
 int pt_texture_pad(pt_ctx* c, const uint8_t* bgra_in, int resolution, int ksize, uint8_t* bgra_out) {

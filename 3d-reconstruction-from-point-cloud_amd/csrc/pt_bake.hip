@@ -17,10 +17,22 @@
 //   * a pixel covered by several triangles keeps the LAST one in (face, triangle) order -- the single-threaded reference's result:
 //     here every covered pixel does one 64-bit atomicMax on a key {face * 256 + triangle + 1, BGRA}; a second pass keeps the BGRA.
 //
+// Object-space normal map ("Normal map"): the same face pass can also write -- or write instead -- a second key
+// plane whose payload is the barycentric mix of the three sub-triangle normals, renormalised PER PIXEL and encoded R = x, G = y, B = z.
+//   * a corner's normal is the mesh vertex record's `normal` (double), an interior point's is the source point's attribute normal
+//     (float, widened, AS UPLOADED: no per-point normalisation; a cloud built without normals holds zeros and its texels fall back);
+//   * both kinds are kept as doubles in LDS next to pc[] (nothing is rounded to float: 11 KB per wave, 44 KB per workgroup);
+//   * a mix of zero or non-finite length encodes (0, 0, 1);   * both planes carry the same key sequence, so the same (face, triangle)
+//     wins a pixel in both;   * the edge padding of the normal plane is the colour plane's (a per-channel maximum: the padded ring is
+//     NOT unit length).
+// The map set is a compile-time property of the kernel (BakeCfg below): the colour-only kernel is the kernel this file always had,
+// instruction for instruction.
+//
 // One wave64 per face (four per workgroup).  Nothing here is bandwidth-critical: the atlas is 64 M pixels, a face a few dozen.
 #include "pt_internal.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -39,6 +51,20 @@ struct BakeWave {
   uint32_t pc[BK_MAXPTS];                 // their colour, r | g << 8 | b << 16
   uint32_t tri[BK_MAXTRI];                // accepted triangles, i | j << 8 | k << 16, in enumeration order
 };
+struct BakeWaveN : BakeWave {              // the instantiations that write the normal plane
+  double pnx[BK_MAXPTS], pny[BK_MAXPTS], pnz[BK_MAXPTS];   // the kept points' normals, as stored (not normalised)
+};
+constexpr int BK_COLOR = 1, BK_NORMAL = 2;   // = PT_MAP_COLOR, PT_MAP_NORMAL
+static_assert(sizeof(BakeWaveN) * BK_WAVES <= 64 * 1024, "the bake's LDS must fit the 64 KB static limit");
+// The face kernel is a template on ONE type: the cloud's coordinate type for the colour-only kernel, WithMaps<coordinate type, map set>
+// for the instantiations that write the normal plane.  A plain second parameter (template <class T, int MAPS = BK_COLOR>) compiles the
+// same colour-only body, but renames the instantiation (bake_faces_kernel<float, 1>), and tools/isa_diff.py pairs kernels of two builds
+// by name and template arguments: this form keeps bake_faces_kernel<float> / <double> paired with every earlier build's.  (The mangled
+// symbol does change -- its parameters are spelled BakeCfg<T>::Real -- which the tool masks.)  The body sits in the kernel itself:
+// behind a device function, even a forced-inline one, the compiler schedules the colour-only kernel differently.
+template <class T, int MAPS> struct WithMaps {};
+template <class C> struct BakeCfg { using Real = C; using Wave = BakeWave; static constexpr int maps = BK_COLOR; };
+template <class T, int M> struct BakeCfg<WithMaps<T, M>> { using Real = T; using Wave = BakeWaveN; static constexpr int maps = M; };
 
 __device__ inline double cross2(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
 __device__ inline bool finite_d(double v) { return v == v && v - v == 0.0; }
@@ -63,9 +89,15 @@ __device__ inline bool in_circumcircle(const double* px, const double* py, int i
   return (double)(os * par) * d > 0.0;
 }
 
+// what a triangle needs for the normal plane: its vertices' normals and the second key plane; nothing in the colour-only instantiation
+struct TriNormals { double v[3][3]; unsigned long long* __restrict__ keys; };
+struct NoNormals {};
+template <int MAPS> using TriN = std::conditional_t<(MAPS & BK_NORMAL) != 0, TriNormals, NoNormals>;
+
 // reference draw_triangle (:66-107), the wave's 64 lanes striding over the pixels of the bounding box that land inside the texture
+template <int MAPS>
 __device__ inline void draw_triangle(const double (&U)[3], const double (&V)[3], const uint32_t (&col)[3], int R, unsigned long long seq,
-                                     unsigned long long* __restrict__ keys, int lane) {
+                                     unsigned long long* __restrict__ keys, int lane, const TriN<MAPS> tn) {
   const double px = U[0] * R, py = V[0] * R, qx = U[1] * R, qy = V[1] * R, rx = U[2] * R, ry = V[2] * R;
   if (!(finite_d(px) && finite_d(py) && finite_d(qx) && finite_d(qy) && finite_d(rx) && finite_d(ry))) return;
   const double A = cross2(qx - px, qy - py, rx - px, ry - py);
@@ -84,33 +116,57 @@ __device__ inline void draw_triangle(const double (&U)[3], const double (&V)[3],
     double b[3];
     bary2((double)x, (double)y, px, py, qx, qy, rx, ry, A, b);
     if (b[0] >= 0 && b[1] >= 0 && b[2] >= 0) {
-      uint32_t bgra = 0xFF000000u;
+      if constexpr ((MAPS & BK_COLOR) != 0) {
+        uint32_t bgra = 0xFF000000u;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {                        // :95-97: double products summed, stored to a float, truncated to a byte
-        const double c0 = (double)((col[0] >> (8 * c)) & 0xFFu), c1 = (double)((col[1] >> (8 * c)) & 0xFFu), c2 = (double)((col[2] >> (8 * c)) & 0xFFu);
-        const float f = (float)((b[0] * c0 + b[1] * c1) + b[2] * c2);
-        const float g = f < 0.f ? 0.f : (f > 255.f ? 255.f : f);
-        bgra |= (uint32_t)g << (8 * (2 - c));              // byte 0 = B, 1 = G, 2 = R
+        for (int c = 0; c < 3; ++c) {                      // :95-97: double products summed, stored to a float, truncated to a byte
+          const double c0 = (double)((col[0] >> (8 * c)) & 0xFFu), c1 = (double)((col[1] >> (8 * c)) & 0xFFu), c2 = (double)((col[2] >> (8 * c)) & 0xFFu);
+          const float f = (float)((b[0] * c0 + b[1] * c1) + b[2] * c2);
+          const float g = f < 0.f ? 0.f : (f > 255.f ? 255.f : f);
+          bgra |= (uint32_t)g << (8 * (2 - c));            // byte 0 = B, 1 = G, 2 = R
+        }
+        atomicMax(&keys[(size_t)(R - j) * (size_t)R + (size_t)i], (seq << 32) | (unsigned long long)bgra);
       }
-      atomicMax(&keys[(size_t)(R - j) * (size_t)R + (size_t)i], (seq << 32) | (unsigned long long)bgra);
+      if constexpr ((MAPS & BK_NORMAL) != 0) {             // the colour mix's shape on the normals, then unit length per pixel
+        double m[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[c] = (b[0] * tn.v[0][c] + b[1] * tn.v[1][c]) + b[2] * tn.v[2][c];
+        const double l = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+        const bool unit = l > 0.0 && finite_d(l);          // zero, NaN, overflowed: straight up
+        uint32_t bgra = 0xFF000000u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double u = unit ? m[c] / l : (c == 2 ? 1.0 : 0.0);
+          const double t = u * 127.5 + 127.5;
+          const double r = fmin(fmax(t + 0.5, 0.0), 255.0);
+          bgra |= (uint32_t)(int)r << (8 * (2 - c));       // byte 0 = z, 1 = y, 2 = x: R = x, G = y, B = z
+        }
+        atomicMax(&tn.keys[(size_t)(R - j) * (size_t)R + (size_t)i], (seq << 32) | (unsigned long long)bgra);
+      }
     }
   }
 }
 
+// one face by one wave.  keys: one zeroed plane of R x R keys per map of the set, the colour plane first
 template <class T>
-__global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const T* __restrict__ sx, const T* __restrict__ sy, const T* __restrict__ sz,
+__global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCfg<T>::Real* __restrict__ sx, const typename BakeCfg<T>::Real* __restrict__ sy,
+                                                           const typename BakeCfg<T>::Real* __restrict__ sz,
                                                            const Attr* __restrict__ attr, uint32_t n, const unsigned char* __restrict__ verts /* 80-B records */,
                                                            uint32_t nv, const int32_t* __restrict__ faces, uint32_t nf,
                                                            const uint32_t* __restrict__ nbr, int k, int R, unsigned long long* __restrict__ keys) {
-  __shared__ BakeWave sh[BK_WAVES];
+  __shared__ typename BakeCfg<T>::Wave sh[BK_WAVES];
   const int lane = threadIdx.x & 63;
   const uint32_t f = blockIdx.x * BK_WAVES + (threadIdx.x >> 6);
   if (f >= nf) return;                                     // whole waves leave; there is no workgroup barrier below
-  BakeWave& W = sh[threadIdx.x >> 6];
+  typename BakeCfg<T>::Wave& W = sh[threadIdx.x >> 6];
   const int32_t f0 = faces[3 * (size_t)f], f1 = faces[3 * (size_t)f + 1], f2 = faces[3 * (size_t)f + 2];
   if (f0 < 0 || f1 < 0 || f2 < 0 || (uint32_t)f0 >= nv || (uint32_t)f1 >= nv || (uint32_t)f2 >= nv) return;      // malformed face
   const int32_t fv[3] = {f0, f1, f2};
   double c3[3][3], cu[3], cv[3];
+  constexpr int MAPS = BakeCfg<T>::maps;
+  constexpr bool NRM = (MAPS & BK_NORMAL) != 0;
+  TriN<MAPS> tn;
+  if constexpr (NRM) tn.keys = (MAPS & BK_COLOR) ? keys + (size_t)R * (size_t)R : keys;
   uint32_t ccol[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -118,6 +174,7 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const T* __restrict__
     const int* ci = reinterpret_cast<const int*>(verts + (size_t)fv[c] * 80 + 48);
     c3[c][0] = d[0]; c3[c][1] = d[1]; c3[c][2] = d[2];
     cu[c] = d[8]; cv[c] = d[9];
+    if constexpr (NRM) { tn.v[c][0] = d[3]; tn.v[c][1] = d[4]; tn.v[c][2] = d[5]; }
     ccol[c] = (uint32_t)min(max(ci[0], 0), 255) | ((uint32_t)min(max(ci[1], 0), 255) << 8) | ((uint32_t)min(max(ci[2], 0), 255) << 16);
   }
   // ---- union of the three neighbour lists, by original index, ascending -----------------------------------------------
@@ -172,6 +229,11 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const T* __restrict__
     W.px[lane] = lane == 0 ? P0x : (lane == 1 ? P1x : P2x);
     W.py[lane] = lane == 0 ? P0y : (lane == 1 ? P1y : P2y);
     W.pu[lane] = cu[lane]; W.pv[lane] = cv[lane]; W.pc[lane] = ccol[lane];
+    if constexpr (NRM) {                                   // (selects, not tn.v[lane]: a lane-indexed register array would live in scratch)
+      W.pnx[lane] = lane == 0 ? tn.v[0][0] : (lane == 1 ? tn.v[1][0] : tn.v[2][0]);
+      W.pny[lane] = lane == 0 ? tn.v[0][1] : (lane == 1 ? tn.v[1][1] : tn.v[2][1]);
+      W.pnz[lane] = lane == 0 ? tn.v[0][2] : (lane == 1 ? tn.v[1][2] : tn.v[2][2]);
+    }
   }
   int np = 3;
   if (frame_ok && A != 0.0 && finite_d(A)) {
@@ -216,6 +278,7 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const T* __restrict__
         const int slot = 3 + (h ? (int)__popcll(m0) + (int)__popcll(m1 & below) : (int)__popcll(m0 & below));
         W.px[slot] = W.cx[e]; W.py[slot] = W.cy[e]; W.pu[slot] = W.cu[e]; W.pv[slot] = W.cv[e];
         W.pc[slot] = attr[W.sorted[e]].rgba & 0xFFFFFFu;
+        if constexpr (NRM) { const Attr a = attr[W.sorted[e]]; W.pnx[slot] = (double)a.nx; W.pny[slot] = (double)a.ny; W.pnz[slot] = (double)a.nz; }
       }
     }
     np = 3 + (int)__popcll(m0) + (int)__popcll(m1);
@@ -224,7 +287,7 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const T* __restrict__
   }
   const unsigned long long seq0 = (unsigned long long)f * 256ull + 1ull;
   if (np == 3) {                                            // no interior points: the face itself (:540-544)
-    draw_triangle(cu, cv, ccol, R, seq0, keys, lane);
+    draw_triangle<MAPS>(cu, cv, ccol, R, seq0, keys, lane, tn);
     return;
   }
   // ---- Delaunay by exhaustion: triples in lexicographic order, lanes over k (:546-581 with the build's definition) --------
@@ -258,7 +321,12 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const T* __restrict__
     const int a = (int)(tr & 0xFFu), b = (int)((tr >> 8) & 0xFFu), c = (int)((tr >> 16) & 0xFFu);
     const double U[3] = {W.pu[a], W.pu[b], W.pu[c]}, V[3] = {W.pv[a], W.pv[b], W.pv[c]};
     const uint32_t col[3] = {W.pc[a], W.pc[b], W.pc[c]};
-    draw_triangle(U, V, col, R, seq0 + (unsigned long long)t, keys, lane);
+    if constexpr (NRM) {
+      tn.v[0][0] = W.pnx[a]; tn.v[0][1] = W.pny[a]; tn.v[0][2] = W.pnz[a];
+      tn.v[1][0] = W.pnx[b]; tn.v[1][1] = W.pny[b]; tn.v[1][2] = W.pnz[b];
+      tn.v[2][0] = W.pnx[c]; tn.v[2][1] = W.pny[c]; tn.v[2][2] = W.pnz[c];
+    }
+    draw_triangle<MAPS>(U, V, col, R, seq0 + (unsigned long long)t, keys, lane, tn);
   }
 }
 
@@ -306,15 +374,18 @@ __global__ __launch_bounds__(BK_WG) void dilate_cols_pad_kernel(const uint32_t* 
 
 template <class T>
 void pt_launch_bake_faces(const T* sx, const T* sy, const T* sz, const Attr* attr, uint32_t n, const void* verts_aos, uint32_t nv, const int32_t* faces,
-                          uint32_t nf, const uint32_t* nbr, int k, int R, unsigned long long* keys, hipStream_t s) {
+                          uint32_t nf, const uint32_t* nbr, int k, int R, int maps, unsigned long long* keys, hipStream_t s) {
   if (!nf) return;
-  hipLaunchKernelGGL(bake_faces_kernel<T>, dim3((nf + BK_WAVES - 1) / BK_WAVES), dim3(BK_WG), 0, s, sx, sy, sz, attr, n, (const unsigned char*)verts_aos, nv,
-                     faces, nf, nbr, k, R, keys);
+  const dim3 grid((nf + BK_WAVES - 1) / BK_WAVES), wg(BK_WG);
+  const unsigned char* verts = (const unsigned char*)verts_aos;
+  if (maps == BK_COLOR) hipLaunchKernelGGL(bake_faces_kernel<T>, grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys);
+  else if (maps == BK_NORMAL) hipLaunchKernelGGL((bake_faces_kernel<WithMaps<T, BK_NORMAL>>), grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys);
+  else hipLaunchKernelGGL((bake_faces_kernel<WithMaps<T, BK_COLOR | BK_NORMAL>>), grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys);
 }
 template void pt_launch_bake_faces<float>(const float*, const float*, const float*, const Attr*, uint32_t, const void*, uint32_t, const int32_t*, uint32_t,
-                                          const uint32_t*, int, int, unsigned long long*, hipStream_t);
+                                          const uint32_t*, int, int, int, unsigned long long*, hipStream_t);
 template void pt_launch_bake_faces<double>(const double*, const double*, const double*, const Attr*, uint32_t, const void*, uint32_t, const int32_t*, uint32_t,
-                                           const uint32_t*, int, int, unsigned long long*, hipStream_t);
+                                           const uint32_t*, int, int, int, unsigned long long*, hipStream_t);
 void pt_launch_bake_resolve(const unsigned long long* keys, uint32_t* bgra, size_t npix, hipStream_t s) {
   if (!npix) return;
   hipLaunchKernelGGL(bake_resolve_kernel, dim3((uint32_t)((npix + BK_WG - 1) / BK_WG)), dim3(BK_WG), 0, s, keys, bgra, npix);

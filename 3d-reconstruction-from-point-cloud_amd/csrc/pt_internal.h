@@ -186,9 +186,12 @@ void pt_launch_iota(uint32_t* p, uint32_t n, hipStream_t s);
 // atomicMax on keys[] (zeroed by the caller) with {face * 256 + triangle + 1, BGRA}; resolve keeps the BGRA of the last triangle.
 // sx/sy/sz: planar source xyz by ORIGINAL index; verts_aos: the mesh's 80-byte reference records (device copy);
 // nbr: the mesh vertices' neighbour lists [nv][k] (original indices).
+// maps (PT_MAP_COLOR | PT_MAP_NORMAL, not 0): which key planes the one launch writes.  keys holds one zeroed plane of R x R keys per
+// map of the set, the colour plane first; the normal plane's payload is the per-pixel renormalised mix of the normals (corners: the
+// records' `normal`; interior points: attr's, as stored) under the same key sequence.  Each plane is resolved and padded on its own.
 template <class T>
 void pt_launch_bake_faces(const T* sx, const T* sy, const T* sz, const Attr* attr, uint32_t n, const void* verts_aos, uint32_t nv, const int32_t* faces,
-                          uint32_t nf, const uint32_t* nbr, int k, int R, unsigned long long* keys, hipStream_t s);
+                          uint32_t nf, const uint32_t* nbr, int k, int R, int maps, unsigned long long* keys, hipStream_t s);
 void pt_launch_bake_resolve(const unsigned long long* keys, uint32_t* bgra, size_t npix, hipStream_t s);
 // edge padding (reference :593-611): out = tex + (dilate(tex, ksize x ksize) & ~alpha), saturating; tmp: R*R words of scratch
 void pt_launch_dilate_pad(const uint32_t* tex, uint32_t* tmp, uint32_t* out, int R, int ksize, hipStream_t s);

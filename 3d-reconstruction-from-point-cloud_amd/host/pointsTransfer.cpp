@@ -14,6 +14,8 @@
 // Optional flags after the two positionals (the reference has none; K and RESOLUTION are its compile-time constants, :128-129):
 //   --k K            neighbours per vertex, default 20            --blend mean|invd2   default mean
 //   --out FILE       default transfer.ply ("" = do not write)      --device D           default 0
+//   --normal-map FILE  also bake the object-space normal map (pt_bake_maps: one face pass for both; with --texture "" the map alone);
+//                    not with --synthetic (no mesh: exit 2); under --gpus N the finalize process bakes it, as it bakes the texture
 //   --texture FILE   default texture.png ("" = no bake)            --resolution R       default 8192
 //   --pad K          edge-padding kernel, default 25 (0 = none)
 //   --neighbors FILE also dump the neighbour indices (binary u32[M][K])
@@ -110,6 +112,7 @@ int main(int argc, char** argv) {
   const std::string pc_file_name = argv[1], mesh_file_name = argv[2];
   int K = 20, device = 0, mode = PT_BLEND_MEAN, ply_threads = 0, resolution = 8192, pad = 25;     // K, RESOLUTION: reference :128-129; 25: :594
   std::string out_name = "transfer.ply", nbr_name, tex_name = "texture.png";                      // texture.png: reference :615
+  std::string nmap_name;                           // --normal-map FILE: the object-space normal map, baked beside the texture in one pt_bake_maps call ("" = none)
   std::string json_name;                           // --json FILE: the phase times of the stdout lines + pt_stats as one JSON object
   int gpus = 0, rank = -1;
   double max_dist = INFINITY;                      // --max-dist R (+inf: off)
@@ -131,6 +134,7 @@ int main(int argc, char** argv) {
     else if (a == "--out") out_name = val();
     else if (a == "--neighbors") nbr_name = val();
     else if (a == "--texture") tex_name = val();
+    else if (a == "--normal-map") nmap_name = val();
     else if (a == "--json") json_name = val();
     else if (a == "--resolution") resolution = std::atoi(val());
     else if (a == "--pad") pad = std::atoi(val());
@@ -156,6 +160,7 @@ int main(int argc, char** argv) {
   if (K < 1 || K > PT_MAX_K) { std::cerr << "--k must be in [1, " << PT_MAX_K << "]" << std::endl; return 2; }
   if (resolution < 1 || resolution > 32768 || pad < 0 || pad > 255 || (pad > 0 && !(pad & 1))) { std::cerr << "--resolution must be in [1, 32768], --pad 0 or odd" << std::endl; return 2; }
   if (!max_dist_ok) { std::cerr << "--max-dist must be a number >= 0" << std::endl; return 2; }
+  if (!nmap_name.empty() && synthetic) { std::cerr << "--normal-map needs a mesh: not with --synthetic" << std::endl; return 2; }
   const bool capped = max_dist < INFINITY;
   // vertices whose list came back empty under the cap (reported on stderr and in --json; the stdout lines stay the reference's)
   auto count_empty = [&](const std::vector<uint32_t>& ids, size_t rows) {
@@ -167,7 +172,7 @@ int main(int argc, char** argv) {
     // the sharded path (host/sharded.h): launcher -> one rank process per GPU -> finalize
     if (gpus < 1 || gpus > 64) { std::cerr << "--gpus must be in [1, 64]" << std::endl; return 2; }
     sharded::Options so;
-    so.cloud = pc_file_name; so.mesh = mesh_file_name; so.out_name = out_name; so.tex_name = tex_name; so.rendezvous = rendezvous;
+    so.cloud = pc_file_name; so.mesh = mesh_file_name; so.out_name = out_name; so.tex_name = tex_name; so.nmap_name = nmap_name; so.rendezvous = rendezvous;
     so.K = K; so.device = device; so.mode = mode; so.ply_threads = ply_threads; so.resolution = resolution; so.pad = pad; so.gpus = gpus; so.rank = rank;
     so.max_dist = max_dist;
     if (rank >= 0) return rank < gpus && !rendezvous.empty() ? sharded::run_rank(so) : 2;
@@ -329,11 +334,13 @@ int main(int argc, char** argv) {
   const double t_blend = since(t_task);
   t_task = clk::now();
   // the reference's face loop after the search (:484-581) and its post-processing (:593-611), on the GPU
-  std::vector<uint8_t> texture;
-  if (!tex_name.empty()) {
-    texture.resize((size_t)resolution * (size_t)resolution * 4);
-    rc = pt_bake_texture(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, idx.data(), K, resolution,
-                         pad, texture.data());
+  std::vector<uint8_t> texture, normal_map;
+  if (!tex_name.empty() || !nmap_name.empty()) {
+    const int maps = (tex_name.empty() ? 0 : PT_MAP_COLOR) | (nmap_name.empty() ? 0 : PT_MAP_NORMAL);      // both in one face pass
+    if (maps & PT_MAP_COLOR) texture.resize((size_t)resolution * (size_t)resolution * 4);
+    if (maps & PT_MAP_NORMAL) normal_map.resize((size_t)resolution * (size_t)resolution * 4);
+    rc = pt_bake_maps(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, idx.data(), K, resolution,
+                      pad, maps, texture.empty() ? nullptr : texture.data(), normal_map.empty() ? nullptr : normal_map.data());
     if (rc != PT_OK) { std::cerr << "pointsTransfer: texture bake failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
   }
   const double t_bake = since(t_task);
@@ -342,6 +349,11 @@ int main(int argc, char** argv) {
   t_task = clk::now();
   if (!tex_name.empty() && !png::write_bgra(tex_name, texture.data(), resolution, resolution)) {
     std::cerr << "pointsTransfer: cannot write " << tex_name << std::endl;
+    pt_ctx_destroy(ctx);
+    return 1;
+  }
+  if (!nmap_name.empty() && !png::write_bgra(nmap_name, normal_map.data(), resolution, resolution)) {
+    std::cerr << "pointsTransfer: cannot write " << nmap_name << std::endl;
     pt_ctx_destroy(ctx);
     return 1;
   }
@@ -372,6 +384,11 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 8; ++i) j << (i ? ", " : "") << st.ms_kernel[i];
     j << "]}";
     if (capped) j << ", \"max_dist\": " << max_dist << ", \"vertices_without_neighbours\": " << n_empty;
+    if (!nmap_name.empty()) {                                       // (the two characters a JSON string cannot hold as they are)
+      j << ", \"normal_map\": \"";
+      for (const char ch : nmap_name) { if (ch == '"' || ch == '\\') j << '\\'; j << ch; }
+      j << "\"";
+    }
     j << "}\n";
     if (!j) std::cerr << "pointsTransfer: cannot write " << json_name << std::endl;
   }

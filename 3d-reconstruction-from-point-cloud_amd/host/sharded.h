@@ -51,7 +51,7 @@ extern char** environ;
 namespace sharded {
 
 struct Options {
-  std::string cloud, mesh, out_name = "transfer.ply", tex_name = "texture.png", rendezvous;
+  std::string cloud, mesh, out_name = "transfer.ply", tex_name = "texture.png", nmap_name, rendezvous;      // nmap_name: --normal-map ("" = none)
   int K = 20, device = 0, mode = PT_BLEND_MEAN, ply_threads = 0, resolution = 8192, pad = 25, gpus = 1, rank = -1;
   double max_dist = INFINITY;       // --max-dist (every rank sets the same cap: pt_api.h "max_dist")
   bool finalize = false;
@@ -59,7 +59,7 @@ struct Options {
 using clk = std::chrono::steady_clock;
 inline double since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
 
-struct RefPoint { uint32_t id; double x, y, z; uint8_t rgb[3]; };
+struct RefPoint { uint32_t id; double x, y, z; uint8_t rgb[3]; float nrm[3]; };      // (nrm: what the normal map mixes)
 
 // free bytes of the file system holding `dir` (0 when it cannot be told)
 inline uint64_t free_bytes(const std::string& dir) {
@@ -308,7 +308,7 @@ inline int run_rank(const Options& o) {
     const Piece& q = cloud.of(id);
     const uint64_t li = id - q.first;
     pts[j].id = id; pts[j].x = q.x[li]; pts[j].y = q.y[li]; pts[j].z = q.z[li];
-    std::memcpy(pts[j].rgb, q.rgb + 3 * li, 3);
+    std::memcpy(pts[j].rgb, q.rgb + 3 * li, 3); std::memcpy(pts[j].nrm, q.nrm + 3 * li, 12);
   }
   const uint64_t hdr[4] = {(uint64_t)mh, (uint64_t)o.K, (uint64_t)pts.size(), (uint64_t)cloud.n};
   const bool ok = write_all(o.rendezvous + "/rank_" + std::to_string(rank) + ".bin",
@@ -357,23 +357,25 @@ inline int run_finalize(const Options& o, WritePly&& write_ply) {
   std::vector<double> cxyz(std::max<size_t>(np, 1) * 3);
   std::vector<uint8_t> crgb(std::max<size_t>(np, 1) * 3);
   std::vector<float> cnrm(std::max<size_t>(np, 1) * 3, 0.f);
-  for (size_t j = 0; j < np; ++j) { cxyz[j] = pts[j].x; cxyz[np + j] = pts[j].y; cxyz[2 * np + j] = pts[j].z; std::memcpy(&crgb[3 * j], pts[j].rgb, 3); }
+  for (size_t j = 0; j < np; ++j) { cxyz[j] = pts[j].x; cxyz[np + j] = pts[j].y; cxyz[2 * np + j] = pts[j].z; std::memcpy(&crgb[3 * j], pts[j].rgb, 3); std::memcpy(&cnrm[3 * j], pts[j].nrm, 12); }
   std::vector<uint32_t> local(idx.size());
   for (size_t e = 0; e < idx.size(); ++e) {
     const auto it = std::lower_bound(pts.begin(), pts.end(), idx[e], [](const RefPoint& a, uint32_t id) { return a.id < id; });
     local[e] = (it != pts.end() && it->id == idx[e]) ? (uint32_t)(it - pts.begin()) : PT_NOIDX;
   }
-  std::vector<uint8_t> texture;
-  if (!o.tex_name.empty()) {
+  std::vector<uint8_t> texture, normal_map;
+  if (!o.tex_name.empty() || !o.nmap_name.empty()) {
     pt_ctx* ctx = nullptr;
     int dev = o.device;
     int rc = pt_ctx_create(&ctx, &dev, 1);
     if (rc != PT_OK) { std::cerr << "pointsTransfer: no usable HIP device for the texture bake" << std::endl; return 1; }
     rc = pt_build_soa(ctx, cxyz.data(), PT_F64, crgb.data(), cnrm.data(), np, 0);
-    texture.resize((size_t)o.resolution * (size_t)o.resolution * 4);
+    const int maps = (o.tex_name.empty() ? 0 : PT_MAP_COLOR) | (o.nmap_name.empty() ? 0 : PT_MAP_NORMAL);      // both in one face pass
+    if (maps & PT_MAP_COLOR) texture.resize((size_t)o.resolution * (size_t)o.resolution * 4);
+    if (maps & PT_MAP_NORMAL) normal_map.resize((size_t)o.resolution * (size_t)o.resolution * 4);
     if (rc == PT_OK)
-      rc = pt_bake_texture(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, local.data(), o.K, o.resolution,
-                           o.pad, texture.data());
+      rc = pt_bake_maps(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, local.data(), o.K, o.resolution,
+                        o.pad, maps, texture.empty() ? nullptr : texture.data(), normal_map.empty() ? nullptr : normal_map.data());
     if (rc != PT_OK) { std::cerr << "pointsTransfer: texture bake failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
     pt_ctx_destroy(ctx);
   }
@@ -385,6 +387,7 @@ inline int run_finalize(const Options& o, WritePly&& write_ply) {
   std::cout << "Draw triangles total time: " << since(t_task) << " seconds" << std::endl;
   t_task = clk::now();
   if (!o.tex_name.empty() && !png::write_bgra(o.tex_name, texture.data(), o.resolution, o.resolution)) { std::cerr << "pointsTransfer: cannot write " << o.tex_name << std::endl; return 1; }
+  if (!o.nmap_name.empty() && !png::write_bgra(o.nmap_name, normal_map.data(), o.resolution, o.resolution)) { std::cerr << "pointsTransfer: cannot write " << o.nmap_name << std::endl; return 1; }
   if (!o.out_name.empty()) write_ply(mesh, rgb, nrm);
   std::cout << "Output time: " << since(t_task) << " seconds" << std::endl;
   return 0;

@@ -350,6 +350,23 @@ class PointsTransfer:
         self._chk(self._L.pt_bake_texture(self._h, _ptr(v), v.shape[0], _ptr(f), f.shape[0], _ptr(nb), nb.shape[1], resolution, pad_ksize, _ptr(out)))
         return out
 
+    def bake_maps(self, mesh_vertices, faces, nbr_idx, resolution=8192, pad_ksize=0, color=True, normals=True):
+        """bake_texture's face pass writing the colour atlas, an object-space normal map (R = x, G = y, B = z, renormalised per texel), or
+        both, in one launch.  The records' `normal` is read for the corners, the resident cloud's uploaded normals for interior points.
+        Returns (bgra or None, normal_bgra or None), each (resolution, resolution, 4) uint8."""
+        if not (color or normals):
+            raise ValueError("bake_maps: ask for at least one of color, normals")
+        v = np.ascontiguousarray(mesh_vertices)
+        assert v.dtype.itemsize == 80
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        nb = np.ascontiguousarray(nbr_idx, dtype=np.uint32)
+        assert nb.ndim == 2 and nb.shape[0] == v.shape[0]
+        col = np.empty((resolution, resolution, 4), np.uint8) if color else None
+        nrm = np.empty((resolution, resolution, 4), np.uint8) if normals else None
+        maps = (capi.MAP_COLOR if color else 0) | (capi.MAP_NORMAL if normals else 0)
+        self._chk(self._L.pt_bake_maps(self._h, _ptr(v), v.shape[0], _ptr(f), f.shape[0], _ptr(nb), nb.shape[1], resolution, pad_ksize, maps, _ptr(col), _ptr(nrm)))
+        return col, nrm
+
     def texture_pad(self, bgra, ksize=25):
         a = np.ascontiguousarray(bgra, dtype=np.uint8)
         assert a.ndim == 3 and a.shape[0] == a.shape[1] and a.shape[2] == 4

@@ -87,7 +87,7 @@ typedef struct pt_stats_t {
   int32_t n_refine;         /* how many times the last build refined its cell size */
   int32_t bbox_guess;       /* last build: 0 the bounding box came from a pass of its own; 1 the grid was laid out from a sampled
                              * box and pass 1 verified it (big clouds); -1 the sampled box was too small and the build was redone */
-  double ms_bake;           /* texture bake (+ edge padding) of the last pt_bake_texture, device time */
+  double ms_bake;           /* texture bake (+ edge padding) of the last pt_bake_texture / pt_bake_maps, device time */
   uint32_t n_nodes;         /* last build: refined ("heavy") cells and sub-cells that carry an 8x8x8 sub-grid (0: none needed) */
   int32_t refine_levels;    /* ... and how many levels deep (<= 3) */
   uint32_t max_cell_points; /* points of the fullest grid cell of the last build (adaptive builds) */
@@ -397,6 +397,27 @@ int  pt_stream_query(pt_ctx*, const void* xyz, int xyz_type, uint64_t n, uint64_
  * by this build (oracle/pt_oracle.c states the definition; INTEGRATION.md lists the points). */
 int  pt_bake_texture(pt_ctx*, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf,
                      const uint32_t* nbr_idx, int k, int resolution, int pad_ksize, uint8_t* bgra_out);
+/* pt_bake_maps: the same face pass writing the colour atlas, an OBJECT-SPACE NORMAL MAP, or both, in one call -- one upload of
+ * vertices, faces and lists and one face launch whatever `maps` is.  `maps` is a non-empty subset of PT_MAP_COLOR | PT_MAP_NORMAL; an
+ * output whose bit is set must be non-null, one whose bit is clear is ignored (may be NULL).  Everything else -- arguments, state
+ * rules, errors, pt_stats_t.ms_bake -- is pt_bake_texture's, and pt_bake_texture IS the PT_MAP_COLOR case of this call (same bytes).
+ * The normal map ("Normal map"): per kept point a normal -- a corner's is the mesh vertex record's `normal`, an
+ * interior point's is the source point's attribute normal as the caller uploaded it (float, widened to double; NOT normalised, so
+ * a longer normal weighs more in the mix) -- and per covered pixel, with the barycentrics b of the colour mix,
+ *   m = (b0 n0 + b1 n1) + b2 n2 per component,  l = sqrt((mx mx + my my) + mz mz),  u = m / l, or (0, 0, 1) unless 0 < l < inf,
+ *   byte = (int)((u * 127.5 + 127.5) + 0.5) clamped to [0, 255],   pixel = {z, y, x, 255} in B, G, R, A order (R = x, G = y, B = z),
+ * all in double, every operation rounded on its own.  The normals are held as doubles throughout: nothing is rounded to float.
+ * The same (face, triangle) wins a pixel in both planes, so their alpha channels are equal; untouched pixels are 0.
+ * The source normals are the ones the caller uploaded: a cloud built WITHOUT normals holds zero records, and a texel between such
+ * points alone falls back to (0, 0, 1) -- estimate the cloud's normals first (nothing here does).  pad_ksize > 0 pads the normal
+ * plane exactly like the colour plane (per-channel maximum of the window under ~alpha): the padded ring is there to keep bilinear
+ * sampling off the background and is NOT unit length -- renormalise in the shader, as for any filtered normal map.
+ * Device memory while the call runs, with P = resolution^2 pixels and m maps: 8 m P (keys) + 4 m P (resolved planes), and with padding
+ * 4 m P + 4 P more -- all held until the planes are copied out: 1.3 GB for one padded map at 8192^2, 2.3 GB for both. */
+enum { PT_MAP_COLOR = 1, PT_MAP_NORMAL = 2 };
+int  pt_bake_maps(pt_ctx*, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf,
+                  const uint32_t* nbr_idx, int k, int resolution, int pad_ksize, int maps,
+                  uint8_t* color_bgra_out, uint8_t* normal_bgra_out);
 /* The edge padding alone (reference :593-611) on a host BGRA image. */
 int  pt_texture_pad(pt_ctx*, const uint8_t* bgra_in, int resolution, int ksize, uint8_t* bgra_out);
 

@@ -1,9 +1,10 @@
 """Timings of the round-2 entry points on one GPU (dev probe; the numbers quoted in DESIGN.md sections 7-9):
-  bake     : pt_bake_texture on a grid mesh over a uniform cloud (faces, resolution, k from argv)
+  bake     : pt_bake_texture, then pt_bake_maps with both maps, on a grid mesh over a uniform cloud (PT_PROBE_BAKE_REPS timed calls each, default 5)
   stream   : pt_stream_query, host-resident cloud in chunks, against the resident search of the same cloud
   exchange : pt_exchange_merge_local, G logical slabs of a uniform cloud (phase times from the library's stats)
 usage: python tools/probe_features.py [bake] [stream] [exchange]"""
 import math
+import os
 import sys
 import time
 
@@ -26,20 +27,29 @@ if "bake" in what:
     with pkg.PointsTransfer(device=0, k_hint=k) as p:
         rng = np.random.default_rng(7)                                           # the cloud samples the sheet the mesh was decimated from
         src = np.stack([rng.random(n, dtype=np.float32), rng.random(n, dtype=np.float32), (0.5 + 1e-4 * rng.standard_normal(n)).astype(np.float32)])
-        p.build(src, rgb=rng.integers(0, 256, (n, 3), dtype=np.uint8))
+        p.build(src, rgb=rng.integers(0, 256, (n, 3), dtype=np.uint8), nrm=rng.standard_normal((n, 3), dtype=np.float32))
         # a textured sheet through the middle of the cloud: (S+1)^2 vertices, 2 S^2 faces, UVs with different scale per axis
         gx, gy = np.meshgrid(np.arange(S + 1) / S, np.arange(S + 1) / S, indexing="xy")
         verts = np.zeros(((S + 1) ** 2,), dtype=pkg.POINT_DTYPE)
         verts["ver"][:, 0] = 0.02 + 0.96 * gx.ravel(); verts["ver"][:, 1] = 0.02 + 0.96 * gy.ravel(); verts["ver"][:, 2] = 0.5
+        verts["normal"][:, 2] = 1.0
         verts["U"] = 0.013 + 0.971 * gx.ravel(); verts["V"] = 0.021 + 0.953 * gy.ravel()
         vid = (np.arange(S)[:, None] * (S + 1) + np.arange(S)[None, :]).ravel()
         faces = np.concatenate([np.stack([vid, vid + 1, vid + S + 2], 1), np.stack([vid, vid + S + 2, vid + S + 1], 1)]).astype(np.int32)
         t0 = now(); idx, _ = p.query(np.ascontiguousarray(verts["ver"].T, dtype=np.float32), k=k); t1 = now()
-        for rep in range(2):
-            t2 = now(); tex = p.bake_texture(verts, faces, idx, resolution=R, pad_ksize=25); t3 = now()
-            st = p.stats()
-            print("bake: %d faces, k=%d, %d^2 atlas: query (host path) %.1f ms, pt_bake_texture wall %.1f ms (device %.2f ms), covered %.1f %%" %
-                  (faces.shape[0], k, R, (t1 - t0) * 1e3, (t3 - t2) * 1e3, st["ms_bake"], 100.0 * float((tex[:, :, 3] > 0).mean())), flush=True)
+        reps = int(os.environ.get("PT_PROBE_BAKE_REPS", "5"))
+        calls = (("pt_bake_texture", lambda: p.bake_texture(verts, faces, idx, resolution=R, pad_ksize=25)),
+                 ("pt_bake_maps (colour + normals)", lambda: p.bake_maps(verts, faces, idx, resolution=R, pad_ksize=25)[0]),
+                 ("pt_bake_maps (normals only)", lambda: p.bake_maps(verts, faces, idx, resolution=R, pad_ksize=25, color=False)[1]))
+        for name, call in calls:
+            dev = []
+            for rep in range(reps + 1):                                              # the first call of each kind is the warm-up
+                t2 = now(); tex = call(); t3 = now()
+                dev.append(p.stats()["ms_bake"])
+                print("bake: %d faces, k=%d, %d^2 atlas: query (host path) %.1f ms, %s wall %.1f ms (device %.2f ms), covered %.1f %%" %
+                      (faces.shape[0], k, R, (t1 - t0) * 1e3, name, (t3 - t2) * 1e3, dev[-1], 100.0 * float((tex[:, :, 3] > 0).mean())), flush=True)
+            d = sorted(dev[1:])
+            print("bake summary: %s device ms over %d calls after one warm-up: min %.2f median %.2f max %.2f" % (name, reps, d[0], d[len(d) // 2], d[-1]), flush=True)
 
 if "stream" in what:
     n, m, k, chunk = 400_000_000, 5_000_000, 8, 100_000_000
