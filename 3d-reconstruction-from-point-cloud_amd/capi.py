@@ -15,6 +15,7 @@ F32, F16, F64 = 0, 1, 2
 DIST_UNIFORM, DIST_CLUSTERED = 0, 1
 BLEND_MEAN, BLEND_INV_D2 = 0, 1
 MAP_COLOR, MAP_NORMAL = 1, 2
+ORIENT_AXIS, ORIENT_VIEWPOINT = 0, 1
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 
 # every symbol include/pt_api.h declares (tests check the .so exports all of them)
@@ -23,7 +24,7 @@ SYMBOLS = [
     "pt_build_aos", "pt_build_soa", "pt_build_soa_indexed", "pt_set_attributes", "pt_set_attributes_range", "pt_set_attributes_local", "pt_build_synth", "pt_rebuild",
     "pt_num_source", "pt_query_aos", "pt_query_soa", "pt_targets_synth", "pt_targets_soa", "pt_targets_aos", "pt_num_targets", "pt_query_resident", "pt_query_blend_resident", "pt_query_resident_host",
     "pt_resident_target_ids", "pt_resident_target_xyz", "pt_resident_source_xyz", "pt_blend", "pt_blend_dev", "pt_blend_weighted", "pt_blend_weighted_dev", "pt_pca_normals",
-    "pt_pca_normals_dev", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
+    "pt_pca_normals_dev", "pt_estimate_normals", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
     "pt_bake_texture", "pt_bake_maps", "pt_texture_pad", "pt_host_alloc", "pt_host_free", "pt_upload_begin", "pt_upload_range", "pt_upload_end", "pt_stream_query",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_comm_abort", "pt_exchange_merge_dev", "pt_exchange_merge_local", "pt_query_exchange_blend",
 ]
@@ -43,6 +44,7 @@ class Stats(C.Structure):
         ("pass1_pooled", C.c_int32), ("stream_skipped", C.c_int32), ("stream_revisited", C.c_int32), ("pass2_pooled", C.c_int32),
         ("uniform_probe", C.c_int32), ("dup_leaves", C.c_int32), ("presort_refine", C.c_int32), ("n_sorts", C.c_int32), ("ordered_input", C.c_int32),
         ("tile_variant", C.c_uint32 * 2), ("tile_retry_blocks", C.c_uint32), ("query_route", C.c_uint32),
+        ("ms_normals", C.c_double), ("n_normal_chunks", C.c_uint32),
     ]
 
 
@@ -110,6 +112,7 @@ def lib():
         "pt_blend_weighted_dev": (i32, [p, p, p, u64, i32, p, p]),
         "pt_pca_normals": (i32, [p, p, u64, i32, p]),
         "pt_pca_normals_dev": (i32, [p, p, u64, i32, p]),
+        "pt_estimate_normals": (i32, [p, i32, i32, C.POINTER(C.c_double), p, i32]),
         "pt_merge_candidates_dev": (i32, [p, p, p, i32, u64, i32, p, p]),
         "pt_slab_need_dev": (i32, [p, p, i32, p, u64, i32, i32, p, i32, i32, p]),
         "pt_pack_requests_dev": (i32, [p, p, i32, p, u64, i32, i32, p, i32, i32, p, p, p]),

@@ -124,6 +124,9 @@ struct pt_ctx {
   bool rec32_valid = false;
   float e_src = 0.f;           // fp64 clouds: largest rounding error of a source coordinate stored as fp32
   DevBuf posattr;              // fp32 clouds: {position, attributes} by original index for the PCA pass, built on first use
+  DevBuf pos16;                // fp32 / fp16 clouds: {x, y, z, 0} by original index, written by every pt_estimate_normals call
+  uint64_t normals_chunk = 8u << 20;      // "normals_chunk": points per chunk of pt_estimate_normals
+  hipEvent_t nev[2] = {nullptr, nullptr}; // ... and its timing (run_query uses ev[0..2] itself)
   bool posattr_valid = false;
   Learned learned;
   bool slab() const { return ids != IdMode::whole; }
@@ -714,8 +717,11 @@ inline bool contrast_last(const pt_ctx* c) {
 struct BlendReq { int mode; float* rgb_out; float* nrm_out; };
 
 // sort the resident targets into cell order and run the k-NN kernel
+// self_first (pt_estimate_normals): the targets are the tm SORTED SOURCE records from *self_first on -- grouped by block already, so they
+// are copied into the target records with their block table (pt_launch_chunk_targets) in place of the target sort; txyz is not read.
+// Everything after the sort is the same for them
 int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const double* bound2_dev, uint32_t* idx_dev, double* d2_dev,
-              const BlendReq* br = nullptr) {
+              const BlendReq* br = nullptr, const uint32_t* self_first = nullptr) {
   c->st.tile_variant[0] = c->st.tile_variant[1] = 0u; c->st.tile_retry_blocks = 0u; c->st.query_route = 0u;
   if (!c->built) return fail(c, PT_ERR_STATE, "query before build");
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [1, %d]", k, PT_MAX_K);
@@ -774,7 +780,8 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
     // was refined): one workgroup per block that HOLDS TARGETS instead of one per block of the grid -- one read-back for the list's length
     const uint32_t* blist = nullptr;
     uint32_t nlist = 0;
-    if (c->tile_sparse == 1 || (c->tile_sparse == 2 && empty_grid)) {
+    // (a chunk of the cloud itself is spatially compact: most blocks of the grid hold none of its targets)
+    if (c->tile_sparse == 1 || (c->tile_sparse == 2 && (empty_grid || (self_first && tm < c->n)))) {
       RES(c, c->tlist, (size_t)c->gp.nblocks * sizeof(uint32_t));
       uint32_t* lcnt = (uint32_t*)c->counter.p + RB_TLIST;
       pt_launch_tblock_list(c->ttb.block_start, (uint32_t)c->gp.nblocks, (uint32_t*)c->tlist.p, lcnt, c->stream);
@@ -915,7 +922,9 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
       if (wave && wave_lists()) wave_pair(tg, bnd, false);
     };
     // targets only need to be grouped by block (tile kernel) -- the cell-level pass is skipped
-    const Rec* tsorted = pt_launch_grid_sort(c->gp, x, x + m, x + 2 * (size_t)m, nullptr, m, (Rec*)c->trec.p, (Rec*)c->trec_tmp.p, nullptr, c->ttb, false, c->stream);
+    const Rec* tsorted = (const Rec*)c->trec.p;
+    if (self_first) pt_launch_chunk_targets<Rec>(src, cell_start, (uint32_t)c->gp.nblocks, *self_first, m, (Rec*)c->trec.p, c->ttb.block_start, c->stream);
+    else tsorted = pt_launch_grid_sort(c->gp, x, x + m, x + 2 * (size_t)m, nullptr, m, (Rec*)c->trec.p, (Rec*)c->trec_tmp.p, nullptr, c->ttb, false, c->stream);
     if (!tsorted) return fail(c, PT_ERR_HIP, "target binning: a launch of the sort failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     if (use_tile) {
@@ -1094,6 +1103,8 @@ int pt_ctx_create(pt_ctx** out, const int* device_ids, int n_devices) {
     if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
   for (auto& e : c->xev)
     if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
+  for (auto& e : c->nev)
+    if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
   if (hipHostMalloc((void**)&c->h_bbox, BB_WORDS * sizeof(uint64_t)) != hipSuccess || hipHostMalloc((void**)&c->h_counter, RB_WORDS * sizeof(uint32_t)) != hipSuccess) {
     delete c;
     return PT_ERR_HIP;
@@ -1109,7 +1120,7 @@ void pt_ctx_destroy(pt_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf* all[] = {&c->in_xyz, &c->in_gidx, &c->attr, &c->rec, &c->rec_tmp, &c->cell_start, &c->stb_mem, &c->t_xyz, &c->t_gidx, &c->trec,
                    &c->trec_tmp, &c->x_xyz, &c->ttb_mem, &c->bbox6, &c->counter, &c->q_idx, &c->q_d2, &c->b_rgb, &c->b_nrm, &c->aos_stage, &c->misc, &c->bounds, &c->todo, &c->posattr, &c->retry, &c->rec32, &c->up_rgb, &c->up_nrm, &c->x_bounds, &c->x_counts, &c->x_matrix, &c->x_off, &c->x_req, &c->x_row, &c->x_rreq,
-                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd};
+                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd, &c->pos16};
   for (DevBuf* b : all) release(c, *b);
   if (c->h_bbox) (void)hipHostFree(c->h_bbox);
   if (c->h_counter) (void)hipHostFree(c->h_counter);
@@ -1120,6 +1131,7 @@ void pt_ctx_destroy(pt_ctx* c) {
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->sev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->xev) if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->nev) if (e) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -1137,6 +1149,11 @@ int pt_set_param(pt_ctx* c, const char* name, double value) {
     if (!(value >= 0.0)) return fail(c, PT_ERR_ARG, "max_dist must be >= 0 (+inf: off), got %g", value);
     c->max_dist = value;
     c->cap2 = value * value;
+    return PT_OK;
+  }
+  if (!strcmp(name, "normals_chunk")) {       // (a setting of pt_estimate_normals: no build depends on it)
+    if (!(value >= 1024.0 && value <= 4294967295.0)) return fail(c, PT_ERR_ARG, "normals_chunk must be in [1024, 2^32), got %g", value);
+    c->normals_chunk = (uint64_t)value;
     return PT_OK;
   }
   c->learned.hint_h = 0.0;             // (whatever changes, the next build searches its cell size afresh)
@@ -1607,6 +1624,73 @@ int pt_pca_normals(pt_ctx* c, const uint32_t* idx, uint64_t m, int k, float* nrm
   c->sync = sync_save;
   if (r != PT_OK) return r;
   if (m) HIPCHK(c, hipMemcpy(nrm_out, c->b_nrm.p, m * 12, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// normals of the resident cloud itself (include/pt_api.h): the sorted records in chunks -> chunk as targets -> the usual search ->
+// PCA of every row, written into the attribute table at the point's original index
+int pt_estimate_normals(pt_ctx* c, int k, int orient, const double* ref, float* nrm_out, int out_on_device) {
+  if (!c) return PT_ERR_ARG;
+  if (!c->built) return fail(c, PT_ERR_STATE, "pt_estimate_normals before a build");
+  if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "pt_estimate_normals needs the whole cloud resident (not a slab)");
+  if (k < 3 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [3, %d]", k, PT_MAX_K);
+  if (orient != PT_ORIENT_AXIS && orient != PT_ORIENT_VIEWPOINT) return fail(c, PT_ERR_ARG, "unknown orientation mode %d", orient);
+  if (orient == PT_ORIENT_VIEWPOINT && !ref) return fail(c, PT_ERR_ARG, "viewpoint orientation needs a viewpoint");
+  NormalOrient o{orient, {0.0, 0.0, 1.0}};
+  if (ref) {
+    for (int a = 0; a < 3; ++a) { if (!std::isfinite(ref[a])) return fail(c, PT_ERR_ARG, "orientation reference is not finite"); o.ref[a] = ref[a]; }
+    if (orient == PT_ORIENT_AXIS && ref[0] == 0.0 && ref[1] == 0.0 && ref[2] == 0.0) return fail(c, PT_ERR_ARG, "orientation axis is zero");
+  }
+  c->st.ms_normals = 0.0; c->st.n_normal_chunks = 0;
+  const uint64_t n = c->n;
+  if (!n) return PT_OK;
+  if (c->has_attr && c->n_total < n) return fail(c, PT_ERR_STATE, "the attribute table holds %llu records, the cloud %llu points", (unsigned long long)c->n_total, (unsigned long long)n);
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t chunk = std::min<uint64_t>(c->normals_chunk, n);
+  const bool f64 = c->src_type == PT_F64;
+  if (!c->has_attr) {                       // a cloud built without attributes: a table of zero colours for the normals to live in
+    RES(c, c->attr, n * sizeof(Attr));
+    HIPCHK(c, hipMemsetAsync(c->attr.p, 0, n * sizeof(Attr), c->stream));
+    c->n_total = n; c->has_attr = true;
+  }
+  c->posattr_valid = false;                 // (its normals are about to change)
+  RES(c, c->q_idx, chunk * (uint64_t)k * sizeof(uint32_t));
+  if (!f64) RES(c, c->pos16, n * 16);
+  if (nrm_out && !out_on_device) RES(c, c->b_nrm, chunk * 12);
+  HIPCHK(c, hipEventRecord(c->nev[0], c->stream));
+  if (!f64) pt_launch_pack_pos16(c->in_xyz.p, c->in_half, (uint32_t)n, c->pos16.p, c->stream);
+  float* dev_out = nrm_out && out_on_device ? nrm_out : nullptr;
+  double ms_copy = 0.0, ms_search = 0.0;
+  uint32_t nchunks = 0;
+  for (uint64_t a = 0; a < n; a += chunk, ++nchunks) {
+    const uint32_t first = (uint32_t)a, m = (uint32_t)std::min<uint64_t>(chunk, n - a);
+    { int r = run_query(c, c->in_xyz.p, c->src_type, m, k, nullptr, (uint32_t*)c->q_idx.p, nullptr, nullptr, &first); if (r != PT_OK) return r; }
+    ms_copy += c->st.ms_sort_targets; ms_search += c->st.ms_query;
+    if (f64) {
+      const double* x = (const double*)c->in_xyz.p;
+      pt_launch_self_pca((const uint32_t*)c->q_idx.p, m, k, (const RecD*)c->rec.p + a, x, x + n, x + 2 * n, (uint32_t)n, o, (Attr*)c->attr.p, dev_out, c->stream);
+    } else {
+      pt_launch_self_pca((const uint32_t*)c->q_idx.p, m, k, (const RecF*)c->rec.p + a, c->pos16.p, (uint32_t)n, o, (Attr*)c->attr.p, dev_out, c->stream);
+    }
+  }
+  HIPCHK(c, hipEventRecord(c->nev[1], c->stream));
+  HIPCHK(c, hipGetLastError());
+  c->st.n_normal_chunks = nchunks;
+  if (c->sync || (nrm_out && !out_on_device)) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->nev[0], c->nev[1]));
+    c->st.ms_normals = ms;
+    if (c->sync) { c->st.ms_sort_targets = ms_copy; c->st.ms_query = ms_search; }      // (sums over the chunks: what is left of ms_normals is the PCA pass)
+  }
+  if (nrm_out && !out_on_device) {          // the host's copy comes from the table, a chunk of records at a time
+    for (uint64_t a = 0; a < n; a += chunk) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - a);
+      pt_launch_attr_normals((const Attr*)c->attr.p, (uint32_t)a, m, (float*)c->b_nrm.p, c->stream);
+      HIPCHK(c, hipMemcpyAsync(nrm_out + 3 * a, c->b_nrm.p, (size_t)m * 12, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
   return PT_OK;
 }
 

@@ -5,10 +5,14 @@
 //   * attribute gather + blend.  The reference's only blend arithmetic is the barycentric colour mix of its
 //     rasteriser (reference src/pointsTransfer.cpp:95-97: weights * colours summed as double products);
 //     the per-vertex k-neighbour blend keeps that shape (out = sum_j w_j * a_j) with build-defined weights;
-//   * PCA normals from the neighbours (BASELINE config 3; no reference counterpart).
+//   * PCA normals from the neighbours (BASELINE config 3; no reference counterpart);
+//   * normals of the resident cloud itself (pt_estimate_normals): a chunk of the sorted records as targets, and the PCA of every
+//     chunk row from its own list, written into the attribute table.
 #include "pt_internal.h"
 
 #include <hip/hip_fp16.h>
+
+#include <algorithm>
 
 namespace {
 
@@ -319,11 +323,14 @@ __global__ __launch_bounds__(WG) void pack_posattr_kernel(const float* __restric
   out[i] = r;
 }
 
-// PCA normal of one target from its neighbours: `fetch(id, p, nrm)` yields the neighbour's position (fp64) and normal
+// The PCA axis of one row of neighbour lists: `fetch(id, p, nrm)` yields the neighbour's position (fp64) and normal.  Returns the number
+// of entries that name a point; with three or more, nn is the (unnormalised) eigenvector of the smallest eigenvalue of their covariance
+// and mn the sum of their normals (has_attr)
 template <class Fetch>
-__device__ inline void pca_one(const uint32_t* __restrict__ idx, uint32_t t, int k, uint32_t n, bool has_attr, float* __restrict__ nrm_out, Fetch fetch) {
+__device__ inline int pca_axis(const uint32_t* __restrict__ idx, uint32_t t, int k, uint32_t n, bool has_attr, double (&nn)[3], double (&mn)[3], Fetch fetch) {
   // one gather pass: moments about the first neighbour (a shift keeps Sum(dd^T) - Sum(d)Sum(d)^T/n free of cancellation)
-  double mn[3] = {0, 0, 0}, sd[3] = {0, 0, 0}, o[3] = {0, 0, 0};
+  double sd[3] = {0, 0, 0}, o[3] = {0, 0, 0};
+  mn[0] = mn[1] = mn[2] = 0.0;
   double cv[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
   int ke = 0;
   // four neighbours' records in flight per thread, consumed in order (as blend_one; a missing neighbour fetches record 0)
@@ -352,8 +359,7 @@ __device__ inline void pca_one(const uint32_t* __restrict__ idx, uint32_t t, int
       if (has_attr) { mn[0] += (double)aq[q][0]; mn[1] += (double)aq[q][1]; mn[2] += (double)aq[q][2]; }
     }
   }
-  float* o3 = nrm_out + 3 * (size_t)t;
-  if (ke < 3) { o3[0] = 0.f; o3[1] = 0.f; o3[2] = 1.f; return; }
+  if (ke < 3) return ke;
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -361,10 +367,19 @@ __device__ inline void pca_one(const uint32_t* __restrict__ idx, uint32_t t, int
   double v[3][3];
   jacobi3(cv, v);
   const double e0 = cv[0][0], e1 = cv[1][1], e2 = cv[2][2];
-  double nn[3];
   if (e0 <= e1 && e0 <= e2) { nn[0] = v[0][0]; nn[1] = v[1][0]; nn[2] = v[2][0]; }
   else if (e1 <= e2) { nn[0] = v[0][1]; nn[1] = v[1][1]; nn[2] = v[2][1]; }
   else { nn[0] = v[0][2]; nn[1] = v[1][2]; nn[2] = v[2][2]; }
+  return ke;
+}
+
+// PCA normal of one target from its neighbours, oriented by the neighbours' stored normals (or +z without a table)
+template <class Fetch>
+__device__ inline void pca_one(const uint32_t* __restrict__ idx, uint32_t t, int k, uint32_t n, bool has_attr, float* __restrict__ nrm_out, Fetch fetch) {
+  double nn[3], mn[3];
+  const int ke = pca_axis(idx, t, k, n, has_attr, nn, mn, fetch);
+  float* o3 = nrm_out + 3 * (size_t)t;
+  if (ke < 3) { o3[0] = 0.f; o3[1] = 0.f; o3[2] = 1.f; return; }
   const double len = sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
   const double ref = has_attr ? (nn[0] * mn[0] + nn[1] * mn[1] + nn[2] * mn[2]) : nn[2];
   const double sgn = (ref < 0 ? -1.0 : 1.0) / len;
@@ -392,6 +407,78 @@ __global__ __launch_bounds__(WG) void pca_pa_kernel(const uint32_t* __restrict__
     p[0] = (double)a.x; p[1] = (double)a.y; p[2] = (double)a.z;
     an[0] = b.x; an[1] = b.y; an[2] = b.z;
   });
+}
+
+// ---- normals of the resident cloud itself (pt_estimate_normals) ----------------------------------------------------------------
+// sorted source records [a, a + m) as target records (id = position in the chunk) + the chunk's block table from the source's cell_start
+template <class Rec>
+__global__ __launch_bounds__(WG) void chunk_targets_kernel(const Rec* __restrict__ src, const uint32_t* __restrict__ cell_start, uint32_t nblocks, uint32_t a,
+                                                           uint32_t m, Rec* __restrict__ tgt, uint32_t* __restrict__ tblock_start) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i < m) { Rec r = src[(size_t)a + i]; r.id = i; tgt[i] = r; }
+  if (i <= nblocks) {
+    const uint32_t s = cell_start[(size_t)i * PT_BLOCK_CELLS];
+    tblock_start[i] = s <= a ? 0u : min(s - a, m);
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(WG) void pack_pos16_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z, uint32_t n, float4* __restrict__ out) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  out[i] = make_float4((float)x[i], (float)y[i], (float)z[i], 0.f);
+}
+
+// orientation and the two writes of one row's normal: the attribute record of the point (colour kept) and the optional output row
+__device__ inline void self_pca_finish(int ke, const double (&nn)[3], const double (&p)[3], const NormalOrient& o, uint32_t id, Attr* __restrict__ attr,
+                                       float* __restrict__ nrm_out) {
+  float r[3] = {0.f, 0.f, 1.f};
+  if (ke >= 3) {
+    const double len = sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
+    const double d[3] = {o.mode ? o.ref[0] - p[0] : o.ref[0], o.mode ? o.ref[1] - p[1] : o.ref[1], o.mode ? o.ref[2] - p[2] : o.ref[2]};
+    const double ref = nn[0] * d[0] + nn[1] * d[1] + nn[2] * d[2];
+    const double sgn = (ref < 0 ? -1.0 : 1.0) / len;
+    r[0] = (float)(nn[0] * sgn); r[1] = (float)(nn[1] * sgn); r[2] = (float)(nn[2] * sgn);
+  }
+  float* a = reinterpret_cast<float*>(attr + id);
+  a[1] = r[0]; a[2] = r[1]; a[3] = r[2];
+  if (nrm_out) { nrm_out[3 * (size_t)id] = r[0]; nrm_out[3 * (size_t)id + 1] = r[1]; nrm_out[3 * (size_t)id + 2] = r[2]; }
+}
+
+// one thread per row of the chunk: row t is the source record rec[t]
+__global__ __launch_bounds__(WG) void self_pca_f32_kernel(const uint32_t* __restrict__ idx, uint32_t m, int k, const RecF* __restrict__ rec,
+                                                          const float4* __restrict__ pos, uint32_t n, NormalOrient o, Attr* __restrict__ attr,
+                                                          float* __restrict__ nrm_out) {
+  const uint32_t t = blockIdx.x * WG + threadIdx.x;
+  if (t >= m) return;
+  const RecF self = rec[t];
+  double nn[3], mn[3];
+  const int ke = pca_axis(idx, t, k, n, false, nn, mn, [&](uint32_t id, double (&p)[3], float (&)[3]) {
+    const float4 a = pos[id];
+    p[0] = (double)a.x; p[1] = (double)a.y; p[2] = (double)a.z;
+  });
+  if (self.id >= n) return;
+  const double p[3] = {(double)self.x, (double)self.y, (double)self.z};
+  self_pca_finish(ke, nn, p, o, self.id, attr, nrm_out);
+}
+__global__ __launch_bounds__(WG) void self_pca_f64_kernel(const uint32_t* __restrict__ idx, uint32_t m, int k, const RecD* __restrict__ rec,
+                                                          const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z, uint32_t n,
+                                                          NormalOrient o, Attr* __restrict__ attr, float* __restrict__ nrm_out) {
+  const uint32_t t = blockIdx.x * WG + threadIdx.x;
+  if (t >= m) return;
+  const RecD self = rec[t];
+  double nn[3], mn[3];
+  const int ke = pca_axis(idx, t, k, n, false, nn, mn, [&](uint32_t id, double (&p)[3], float (&)[3]) { p[0] = x[id]; p[1] = y[id]; p[2] = z[id]; });
+  if (self.id >= n) return;
+  const double p[3] = {self.x, self.y, self.z};
+  self_pca_finish(ke, nn, p, o, self.id, attr, nrm_out);
+}
+
+__global__ __launch_bounds__(WG) void attr_normals_kernel(const Attr* __restrict__ attr, uint32_t first, uint32_t count, float* __restrict__ out) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= count) return;
+  const Attr a = attr[(size_t)first + i];
+  out[3 * (size_t)i] = a.nx; out[3 * (size_t)i + 1] = a.ny; out[3 * (size_t)i + 2] = a.nz;
 }
 
 // fp16 planar xyz -> fp32 planar xyz (exact widening): fp16 clouds run through the fp32 path unchanged
@@ -498,4 +585,28 @@ void pt_launch_half_to_float(const void* in_half, float* out, uint64_t count, hi
 void pt_launch_float_to_double(const float* in, double* out, uint64_t count, hipStream_t s) {
   if (!count) return;
   hipLaunchKernelGGL(float_to_double_kernel, dim3((uint32_t)((count + WG - 1) / WG)), dim3(WG), 0, s, in, out, count);
+}
+template <class Rec>
+void pt_launch_chunk_targets(const Rec* src, const uint32_t* cell_start, uint32_t nblocks, uint32_t a, uint32_t m, Rec* tgt, uint32_t* tblock_start, hipStream_t s) {
+  hipLaunchKernelGGL(chunk_targets_kernel<Rec>, grid_for(std::max(m, nblocks + 1)), dim3(WG), 0, s, src, cell_start, nblocks, a, m, tgt, tblock_start);
+}
+template void pt_launch_chunk_targets<RecF>(const RecF*, const uint32_t*, uint32_t, uint32_t, uint32_t, RecF*, uint32_t*, hipStream_t);
+template void pt_launch_chunk_targets<RecD>(const RecD*, const uint32_t*, uint32_t, uint32_t, uint32_t, RecD*, uint32_t*, hipStream_t);
+void pt_launch_pack_pos16(const void* xyz_planar, bool half, uint32_t n, void* out, hipStream_t s) {
+  if (!n) return;
+  if (half) { const __half* x = (const __half*)xyz_planar; hipLaunchKernelGGL(pack_pos16_kernel<__half>, grid_for(n), dim3(WG), 0, s, x, x + n, x + 2 * (size_t)n, n, (float4*)out); }
+  else { const float* x = (const float*)xyz_planar; hipLaunchKernelGGL(pack_pos16_kernel<float>, grid_for(n), dim3(WG), 0, s, x, x + n, x + 2 * (size_t)n, n, (float4*)out); }
+}
+void pt_launch_self_pca(const uint32_t* idx, uint32_t m, int k, const RecF* rec, const void* pos16, uint32_t n, const NormalOrient& o, Attr* attr, float* nrm_out, hipStream_t s) {
+  if (!m) return;
+  hipLaunchKernelGGL(self_pca_f32_kernel, grid_for(m), dim3(WG), 0, s, idx, m, k, rec, (const float4*)pos16, n, o, attr, nrm_out);
+}
+void pt_launch_self_pca(const uint32_t* idx, uint32_t m, int k, const RecD* rec, const double* x, const double* y, const double* z, uint32_t n, const NormalOrient& o, Attr* attr,
+                        float* nrm_out, hipStream_t s) {
+  if (!m) return;
+  hipLaunchKernelGGL(self_pca_f64_kernel, grid_for(m), dim3(WG), 0, s, idx, m, k, rec, x, y, z, n, o, attr, nrm_out);
+}
+void pt_launch_attr_normals(const Attr* attr, uint32_t first, uint32_t count, float* out, hipStream_t s) {
+  if (!count) return;
+  hipLaunchKernelGGL(attr_normals_kernel, grid_for(count), dim3(WG), 0, s, attr, first, count, out);
 }

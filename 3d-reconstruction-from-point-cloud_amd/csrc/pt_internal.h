@@ -180,6 +180,24 @@ void pt_launch_pca(const uint32_t* idx, uint32_t m, int k, const T* x, const T* 
 void pt_launch_pack_posattr(const float* x, const float* y, const float* z, const Attr* attr, uint32_t n, void* out, hipStream_t s);
 void pt_launch_pca_posattr(const uint32_t* idx, uint32_t m, int k, const void* posattr, uint32_t n, int has_attr, float* nrm_out, hipStream_t s);
 void pt_launch_iota(uint32_t* p, uint32_t n, hipStream_t s);
+// ---- normals of the resident cloud itself (pt_estimate_normals; kernels in pt_attr.hip) --------------------------
+// A chunk [a, a + m) of the SORTED source records as block-grouped target records: tgt[i] = src[a + i] with id = i (records sorted by
+// cell are grouped by block already), and the chunk's block table tblock_start[b] = clamp(cell_start[b * 512] - a, 0, m) for
+// b in [0, nblocks] -- what a target sort would have produced, without the sort
+template <class Rec>
+void pt_launch_chunk_targets(const Rec* src, const uint32_t* cell_start, uint32_t nblocks, uint32_t a, uint32_t m, Rec* tgt, uint32_t* tblock_start, hipStream_t s);
+// fp32 / fp16 clouds: 16-byte {x, y, z, 0} records by original index -- what the pass below gathers per neighbour (half: xyz is fp16)
+void pt_launch_pack_pos16(const void* xyz_planar, bool half, uint32_t n, void* out, hipStream_t s);
+// how a normal is oriented: mode 0 dot(n, ref) >= 0, mode 1 dot(n, ref - p) >= 0 with p the point itself (include/pt_api.h, pt_orient_mode)
+struct NormalOrient { int mode; double ref[3]; };
+// PCA normal of the chunk's rows from their own neighbour lists idx[m][k] (pca_one's arithmetic): row t belongs to the source record
+// rec[t] (rec = the sorted records + a); the result goes to attr[rec[t].id].{nx, ny, nz} (colour kept) and, when nrm_out is given, to
+// nrm_out[rec[t].id].  pos16: the table above (RecF); x, y, z: the cloud's planar doubles by original index (RecD)
+void pt_launch_self_pca(const uint32_t* idx, uint32_t m, int k, const RecF* rec, const void* pos16, uint32_t n, const NormalOrient& o, Attr* attr, float* nrm_out, hipStream_t s);
+void pt_launch_self_pca(const uint32_t* idx, uint32_t m, int k, const RecD* rec, const double* x, const double* y, const double* z, uint32_t n, const NormalOrient& o, Attr* attr,
+                        float* nrm_out, hipStream_t s);
+// out[i][3] = the normals of the attribute records [first, first + count)
+void pt_launch_attr_normals(const Attr* attr, uint32_t first, uint32_t count, float* out, hipStream_t s);
 
 // ---- pt_bake.hip ------------------------------------------------------------------------------
 // per-face texture bake (reference src/pointsTransfer.cpp:466-581, :66-107): every covered pixel of the R x R atlas does an

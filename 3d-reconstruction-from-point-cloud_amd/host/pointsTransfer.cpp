@@ -25,6 +25,10 @@
 //   --max-dist R     neighbours farther than R (cloud units, R >= 0) are ignored: a vertex with no cloud point within R keeps its own
 //                    mesh colour and normal in transfer.ply, and the texture is baked from the capped lists (pt_api.h "max_dist");
 //                    stderr reports how many vertices had none, --json adds max_dist and vertices_without_neighbours
+//   --estimate-normals K  after the build and before the search, estimate the CLOUD's normals from every point's K nearest neighbours
+//                    (pt_estimate_normals, K in 3..32) in place of the ones the file carries: the blended vertex normals, transfer.ply
+//                    and --normal-map then use them.  --viewpoint X Y Z orients them towards that point (default: +z).  Not with
+//                    --synthetic, not with --gpus N > 1 (the pass needs the whole cloud on one GPU; --gpus 1 runs unsharded): exit 2
 // There is no CPU path: without a usable GPU the tool reports the error and exits non-zero.
 #include <chrono>
 #include <cmath>
@@ -118,6 +122,9 @@ int main(int argc, char** argv) {
   double max_dist = INFINITY;                      // --max-dist R (+inf: off)
   bool max_dist_ok = true;
   bool finalize = false;
+  int est_k = 0;                                   // --estimate-normals K (0: off)
+  bool est_given = false, vp_given = false, vp_ok = true;
+  double viewpoint[3] = {0.0, 0.0, 0.0};           // --viewpoint X Y Z
   std::string rendezvous;
   // --synthetic N M SEED [--clustered] [--xyz f32|f16|f64]: SURVEY.md Appendix C's generator instead of the two files (the positional
   // arguments are ignored): the BASELINE configurations run through this binary without a cloud on disk -- no mesh, so no texture
@@ -154,6 +161,16 @@ int main(int argc, char** argv) {
       max_dist = std::strtod(v, &end);
       max_dist_ok = *v && end && !*end && max_dist >= 0.0;       // (NaN fails the comparison)
     }
+    else if (a == "--estimate-normals") { est_k = std::atoi(val()); est_given = true; }
+    else if (a == "--viewpoint") {
+      vp_given = true;
+      for (int q = 0; q < 3; ++q) {
+        const char* v = val();
+        char* end = nullptr;
+        viewpoint[q] = std::strtod(v, &end);
+        vp_ok = vp_ok && *v && end && !*end && std::isfinite(viewpoint[q]);
+      }
+    }
     else { std::cerr << "unknown option " << a << std::endl; return 2; }
     for (int j = i_before; j <= i; ++j) passthrough.push_back(argv[j]);
   }
@@ -161,6 +178,12 @@ int main(int argc, char** argv) {
   if (resolution < 1 || resolution > 32768 || pad < 0 || pad > 255 || (pad > 0 && !(pad & 1))) { std::cerr << "--resolution must be in [1, 32768], --pad 0 or odd" << std::endl; return 2; }
   if (!max_dist_ok) { std::cerr << "--max-dist must be a number >= 0" << std::endl; return 2; }
   if (!nmap_name.empty() && synthetic) { std::cerr << "--normal-map needs a mesh: not with --synthetic" << std::endl; return 2; }
+  if (est_given && (est_k < 3 || est_k > PT_MAX_K)) { std::cerr << "--estimate-normals must be in [3, " << PT_MAX_K << "]" << std::endl; return 2; }
+  if (vp_given && !est_given) { std::cerr << "--viewpoint needs --estimate-normals" << std::endl; return 2; }
+  if (vp_given && !vp_ok) { std::cerr << "--viewpoint needs three finite numbers" << std::endl; return 2; }
+  if (est_given && synthetic) { std::cerr << "--estimate-normals / --viewpoint: not with --synthetic (the generated cloud has normals)" << std::endl; return 2; }
+  if (est_given && (gpus > 1 || rank >= 0 || finalize)) { std::cerr << "--estimate-normals / --viewpoint: not with --gpus N > 1 (the pass needs the whole cloud on one GPU)" << std::endl; return 2; }
+  if (est_given && gpus == 1) gpus = 0;            // (one GPU: the unsharded path, which holds the whole cloud)
   const bool capped = max_dist < INFINITY;
   // vertices whose list came back empty under the cap (reported on stderr and in --json; the stdout lines stay the reference's)
   auto count_empty = [&](const std::vector<uint32_t>& ids, size_t rows) {
@@ -298,6 +321,12 @@ int main(int argc, char** argv) {
   if (rc == PT_OK) rc = pt_upload_end(ctx);
   free_pinned();
   if (rc != PT_OK) { std::cerr << "pointsTransfer: build failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+  if (est_given) {                                 // (inside the build's line: stdout keeps the reference's set of lines)
+    rc = pt_estimate_normals(ctx, est_k, vp_given ? PT_ORIENT_VIEWPOINT : PT_ORIENT_AXIS, vp_given ? viewpoint : nullptr, nullptr, 0);
+    if (rc != PT_OK) { std::cerr << "pointsTransfer: normal estimation failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+    pt_stats_t sn;
+    if (pt_stats(ctx, &sn) == PT_OK) std::cerr << "[pt_hip] estimated the cloud's normals (k = " << est_k << ") in " << sn.ms_normals << " ms, " << sn.n_normal_chunks << " chunks (device time)" << std::endl;
+  }
   const double t_build = since(t_task);
   std::cout << "Built Kd tree in: " << t_build << " seconds" << std::endl;   // the line's wording is the contract
   t_task = clk::now();

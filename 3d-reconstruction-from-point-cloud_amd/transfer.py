@@ -280,6 +280,33 @@ class PointsTransfer:
         self._adopt_torch_stream()
         self._chk(self._L.pt_pca_normals_dev(self._h, _ptr(idx_dev), m, k, _ptr(nrm_out_dev)))
 
+    @staticmethod
+    def _orientation(viewpoint, axis):
+        if viewpoint is not None and axis is not None:
+            raise ValueError("estimate_normals: give a viewpoint or an axis, not both")
+        ref = viewpoint if viewpoint is not None else axis
+        if ref is None:
+            return capi.ORIENT_AXIS, None                      # +z
+        r = np.asarray(ref, np.float64).reshape(-1)
+        if r.shape != (3,):
+            raise ValueError("estimate_normals: viewpoint / axis must have three components")
+        return (capi.ORIENT_VIEWPOINT if viewpoint is not None else capi.ORIENT_AXIS), (C.c_double * 3)(*r)
+
+    def estimate_normals(self, k=16, viewpoint=None, axis=None):
+        """Normals of the resident cloud itself, from every point's own k nearest neighbours (PCA), written into the resident attribute
+        table (colours kept) and returned as an (n, 3) float32 array by original index.  Orientation: towards `viewpoint` (x, y, z),
+        or along `axis` (default +z).  The cloud is walked in chunks of set_param("normals_chunk", c) points."""
+        mode, ref = self._orientation(viewpoint, axis)
+        out = np.empty((self.num_source, 3), np.float32)
+        self._chk(self._L.pt_estimate_normals(self._h, k, mode, ref, _ptr(out), 0))
+        return out
+
+    def estimate_normals_dev(self, k, nrm_out_dev, viewpoint=None, axis=None):
+        """The same with the (n, 3) float32 result written to a device buffer (None: into the attribute table only)."""
+        mode, ref = self._orientation(viewpoint, axis)
+        self._adopt_torch_stream()
+        self._chk(self._L.pt_estimate_normals(self._h, k, mode, ref, _ptr(nrm_out_dev), 1))
+
     # -- native slab exchange over RCCL (SURVEY.md 8e) ---------------------------------------------
     @staticmethod
     def comm_unique_id():

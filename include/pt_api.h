@@ -120,6 +120,8 @@ typedef struct pt_stats_t {
   uint32_t tile_retry_blocks; /* blocks the retry launch took (0: none, or no two-per-CU geometry ran) */
   uint32_t query_route;     /* PT_ROUTE_* bits: the kernels the last query launched (a launch over a device-side list counts even when the list
                              * turns out empty -- its length stays on the device) */
+  double ms_normals;        /* pt_estimate_normals: device time of the last call, every chunk's copy, search and PCA included (HIP events) */
+  uint32_t n_normal_chunks; /* ... and the number of chunks it walked the cloud in */
 } pt_stats_t;
 enum {
   PT_ROUTE_TILE = 1,        /* the LDS tile kernel */
@@ -170,7 +172,9 @@ int  pt_set_stream(pt_ctx*, void* hip_stream);
  * wave kernel takes what it leaves; 0, default: a wave per target -- measured faster), "local_ids" (1: the next slab build -- ascending
  * global indices, or a slab pt_build_synth generates -- keeps positions in its records and its own attribute records only; see
  * pt_set_attributes_local), "presort_refine" (1, default: the first build of a big cloud the sample finds non-uniform refines its cell size
- * from the sample's bound on the points per occupied cell, before the first sort; 0: after it, from the sort's count -- round 3's behaviour).
+ * from the sample's bound on the points per occupied cell, before the first sort; 0: after it, from the sort's count -- round 3's behaviour),
+ * "normals_chunk" (points per chunk of pt_estimate_normals, which bounds its scratch memory; default 8 Mi, at least 1024 -- PT_ERR_ARG
+ * below that; small values make a small cloud take many chunks, which is what tests use it for).
  *
  * "max_dist" r (cloud units; r >= 0, +inf = off, the default; NaN or r < 0: PT_ERR_ARG): neighbours farther than r are not returned.
  * R2 = r * r is computed once in double, and a source point is in reach iff d2 <= R2 (d2 the metric above; inclusive, like
@@ -287,6 +291,33 @@ int  pt_blend_weighted_dev(pt_ctx*, const uint32_t* idx_dev, const double* w_dev
  * blends, PCA writes every row. */
 int  pt_pca_normals(pt_ctx*, const uint32_t* idx, uint64_t m, int k, float* nrm_out);
 int  pt_pca_normals_dev(pt_ctx*, const uint32_t* idx_dev, uint64_t m, int k, float* nrm_out_dev);
+/* pt_estimate_normals: normals for a resident cloud that ships without them (or whose normals are to be replaced), written into the
+ * resident attribute table.  Needs a built, whole cloud: PT_ERR_STATE before a build, PT_ERR_UNSUPPORTED on a slab context
+ * (pt_build_soa_indexed, a slab of pt_build_synth, "local_ids"), like PCA.  fp32, fp16 and fp64 clouds alike.
+ * The normal of source point i:
+ *   - take the neighbour list a pt_query_* call with the same k returns for a target at point i's own position, against the resident
+ *     cloud: the k nearest source points under (d2, index) -- i itself, or a lower-indexed duplicate in front of it, among them -- and
+ *     under a "max_dist" cap the capped list;
+ *   - the unit eigenvector of the smallest eigenvalue of the covariance of those points: pt_pca_normals' definition to the letter, "fewer
+ *     than three entries -> (0, 0, 1)" included (such a row is not oriented either).
+ * Orientation (`orient`, a pt_orient_mode; the stored normals are never read, so the in-place write has no read / write hazard):
+ *   PT_ORIENT_AXIS       dot(n, ref) >= 0; ref == NULL means (0, 0, 1), the convention of pt_pca_normals without a table;
+ *   PT_ORIENT_VIEWPOINT  dot(n, ref - p_i) >= 0, evaluated in double; ref must not be NULL.
+ * A dot product of exactly 0 keeps the eigenvector's sign as computed (pt_pca_normals' `ref < 0 ? -1 : 1`).  A non-finite ref, a zero
+ * ref in AXIS mode, a NULL ref in VIEWPOINT mode, an unknown mode, or k outside [3, PT_MAX_K]: PT_ERR_ARG.
+ * The result goes into the attribute table at the point's original index; colours are kept.  A cloud built without attributes gets a
+ * table with zero colours, so blends, pt_bake_maps and a later pt_pca_normals -- which then ORIENTS BY THESE NORMALS instead of +z --
+ * see a resident table afterwards.  nrm_out (may be NULL) receives float[n][3] by original index, in host or device memory according
+ * to out_on_device.  n = 0: PT_OK, nothing is written.  Resident targets (pt_targets_*) are left as they were; the statistics of "the
+ * last query" describe the last chunk's search, with ms_sort_targets / ms_query summed over the chunks ("sync" = 1).
+ * Memory: the lists never exist for the whole cloud.  The pass walks the sorted records in chunks of c = "normals_chunk" points: each
+ * chunk's records become the target records as they are (no target sort, nothing re-uploaded) and are searched by the usual routes.
+ * Beyond the attribute table (16 n) and, for fp32 / fp16 clouds, one position table by original index (16 n), the scratch is
+ *   c * (4 k + 2 r + 9) bytes (lists, two target record buffers of r = 16 or 32 bytes, leftover list, wave marks), 8 c more under a
+ *   cap, 12 c more for a host nrm_out, plus 20 bytes per 512-cell grid block for the block tables -- nothing that grows with n * k.
+ * pt_stats_t: ms_normals, n_normal_chunks. */
+typedef enum { PT_ORIENT_AXIS = 0, PT_ORIENT_VIEWPOINT = 1 } pt_orient_mode;
+int  pt_estimate_normals(pt_ctx*, int k, int orient, const double ref3_or_null[3], float* nrm_out_or_null, int out_on_device);
 
 /* ---- multi-GPU merge ---------------------------------------------------------- */
 /* G-way merge of candidate lists under (d2, idx): lists are [g][m][k] device arrays. */
@@ -409,7 +440,7 @@ int  pt_bake_texture(pt_ctx*, const pt_point* mesh_vertices, uint64_t nv, const 
  * all in double, every operation rounded on its own.  The normals are held as doubles throughout: nothing is rounded to float.
  * The same (face, triangle) wins a pixel in both planes, so their alpha channels are equal; untouched pixels are 0.
  * The source normals are the ones the caller uploaded: a cloud built WITHOUT normals holds zero records, and a texel between such
- * points alone falls back to (0, 0, 1) -- estimate the cloud's normals first (nothing here does).  pad_ksize > 0 pads the normal
+ * points alone falls back to (0, 0, 1) -- estimate the cloud's normals first (pt_estimate_normals).  pad_ksize > 0 pads the normal
  * plane exactly like the colour plane (per-channel maximum of the window under ~alpha): the padded ring is there to keep bilinear
  * sampling off the background and is NOT unit length -- renormalise in the shader, as for any filtered normal map.
  * Device memory while the call runs, with P = resolution^2 pixels and m maps: 8 m P (keys) + 4 m P (resolved planes), and with padding
