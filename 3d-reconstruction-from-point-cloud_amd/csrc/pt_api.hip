@@ -98,6 +98,8 @@ struct pt_ctx {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t switch_ev = nullptr;   // orders a newly set stream behind what is still queued on the previous one (switch_stream)
+  bool in_flight = false;           // "sync" 0: a call has returned with work queued that no host wait of this context has covered since
   hipEvent_t sev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // per-kernel marks of the source sort
   std::string err;
   double rho = 4.0;            // points per cell: 10^3-cell regions of ~4000 records let TWO tile workgroups share a CU
@@ -238,8 +240,32 @@ void release(pt_ctx* c, DevBuf& b) {
 size_t tsize(int t) { return t == PT_F64 ? 8 : 4; }
 size_t recsize(int t) { return t == PT_F64 ? sizeof(RecD) : sizeof(RecF); }
 
-int finish(pt_ctx* c) {
-  if (c->sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+// The end of every entry point that may return with work queued, and the only place in_flight changes: `wait` drains the stream and
+// forgets, otherwise the context remembers that it has left work queued (switch_stream).  Not told: a call that fails part-way (its
+// error is the caller's signal to pt_synchronize or drop the context) and pt_upload_range, whose copies pt_upload_end waits for.
+int settle(pt_ctx* c, bool wait) {
+  if (wait) HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->in_flight = !wait;
+  return PT_OK;
+}
+#define SETTLE(c, wait)                          \
+  do {                                           \
+    int r_ = settle((c), (wait));                \
+    if (r_ != PT_OK) return r_;                  \
+  } while (0)
+int finish(pt_ctx* c) { return settle(c, c->sync != 0); }
+
+// pt_set_stream / "own_stream": from now on the context's work goes to stream `s`.  What it queued on the stream it leaves and no host wait
+// has covered yet ("sync" 0) may still be running there -- a scratch buffer being read, a list a later call consumes -- so the new stream
+// waits for it: one event on the old stream, one wait on the new one, nothing on the host.  Draining the new stream then covers both.
+int switch_stream(pt_ctx* c, hipStream_t s) {
+  if (s == c->stream) return PT_OK;
+  if (c->in_flight) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventRecord(c->switch_ev, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->switch_ev, 0));
+  }
+  c->stream = s;
   return PT_OK;
 }
 
@@ -677,8 +703,8 @@ int rebuild(pt_ctx* c) {
   (void)ncells;
   const uint64_t s = tsize(c->src_type) * 3;
   c->st.bytes_alg_build = c->n * (2 * s + 4);
+  SETTLE(c, c->sync != 0);
   if (c->sync) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     c->st.ms_build = ms;
@@ -957,8 +983,8 @@ int run_query(pt_ctx* c, const void* txyz, int ttype, uint64_t tm, int k, const 
   c->st.k = k;
   const uint64_t s = tsize(c->src_type) * 3;
   c->st.bytes_alg_query = c->n * s + (uint64_t)m * s + (uint64_t)m * k * 16 + (uint64_t)m * (4 * (uint64_t)k + 24);
+  SETTLE(c, c->sync != 0);
   if (c->sync) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     float a = 0, b = 0;
     HIPCHK(c, hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
     HIPCHK(c, hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
@@ -1105,6 +1131,7 @@ int pt_ctx_create(pt_ctx** out, const int* device_ids, int n_devices) {
     if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
   for (auto& e : c->nev)
     if (hipEventCreate(&e) != hipSuccess) { delete c; return PT_ERR_HIP; }
+  if (hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming) != hipSuccess) { delete c; return PT_ERR_HIP; }
   if (hipHostMalloc((void**)&c->h_bbox, BB_WORDS * sizeof(uint64_t)) != hipSuccess || hipHostMalloc((void**)&c->h_counter, RB_WORDS * sizeof(uint32_t)) != hipSuccess) {
     delete c;
     return PT_ERR_HIP;
@@ -1132,14 +1159,14 @@ void pt_ctx_destroy(pt_ctx* c) {
   for (auto& e : c->sev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->xev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->nev) if (e) (void)hipEventDestroy(e);
+  if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
 
 int pt_set_stream(pt_ctx* c, void* hip_stream) {
   if (!c) return PT_ERR_ARG;
-  c->stream = (hipStream_t)hip_stream;    // NULL is HIP's default stream (what torch uses unless told otherwise)
-  return PT_OK;
+  return switch_stream(c, (hipStream_t)hip_stream);    // NULL is HIP's default stream (what torch uses unless told otherwise)
 }
 
 int pt_set_param(pt_ctx* c, const char* name, double value) {
@@ -1188,7 +1215,7 @@ int pt_set_param(pt_ctx* c, const char* name, double value) {
   if (!strcmp(name, "presort_refine")) { c->presort_refine = value != 0; return PT_OK; }
   if (!strcmp(name, "pool_min_points")) { c->pool_min_points = value < 0 ? 0 : (uint64_t)value; c->learned.pool_ok = true; return PT_OK; }   // pooled pass 1 from this size up (0: never)
   if (!strcmp(name, "guess_min_points")) { c->guess_min_points = value < 1 ? 1 : (uint64_t)value; return PT_OK; }   // sampled-bbox builds from this size up   // 0 group kernel only, 1 auto, 2 small tiles, 3 large tiles
-  if (!strcmp(name, "own_stream")) { if (value != 0) c->stream = c->own_stream; return PT_OK; }
+  if (!strcmp(name, "own_stream")) return value != 0 ? switch_stream(c, c->own_stream) : PT_OK;
   return fail(c, PT_ERR_ARG, "unknown parameter '%s'", name);
 }
 
@@ -1203,8 +1230,7 @@ int pt_stats(pt_ctx* c, pt_stats_t* out) {
 
 int pt_synchronize(pt_ctx* c) {
   if (!c) return PT_ERR_ARG;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return PT_OK;
+  return settle(c, true);
 }
 
 uint64_t pt_num_source(pt_ctx* c) { return c ? c->n : 0; }
@@ -1537,8 +1563,8 @@ int pt_blend_dev(pt_ctx* c, const uint32_t* idx_dev, const double* d2_dev_or_nul
   pt_launch_blend(idx_dev, d2_dev_or_null, (uint32_t)m, k, mode, (const Attr*)c->attr.p, (uint32_t)c->n_total, rgb_out_dev, nrm_out_dev, c->stream, c->capped());
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
+  SETTLE(c, c->sync != 0);
   if (c->sync) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     c->st.ms_blend = ms;
@@ -1601,8 +1627,8 @@ int pt_pca_normals_dev(pt_ctx* c, const uint32_t* idx_dev, uint64_t m, int k, fl
   else { const double* x = (const double*)c->in_xyz.p; pt_launch_pca<double>(idx_dev, (uint32_t)m, k, x, x + c->n, x + 2 * c->n, (uint32_t)c->n, at, nrm_out_dev, c->stream); }
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
+  SETTLE(c, c->sync != 0);
   if (c->sync) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     c->st.ms_pca = ms;
@@ -1676,8 +1702,8 @@ int pt_estimate_normals(pt_ctx* c, int k, int orient, const double* ref, float* 
   HIPCHK(c, hipEventRecord(c->nev[1], c->stream));
   HIPCHK(c, hipGetLastError());
   c->st.n_normal_chunks = nchunks;
+  SETTLE(c, c->sync || (nrm_out && !out_on_device));
   if (c->sync || (nrm_out && !out_on_device)) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->nev[0], c->nev[1]));
     c->st.ms_normals = ms;
@@ -2225,8 +2251,8 @@ int pt_exchange_merge_dev(pt_ctx* c, const void* tgt_xyz_dev, int xyz_type, uint
     const uint64_t cand = c->attr_local() ? 28 : 12;        // (index + distance, + the attribute record when the table is sharded)
     st->bytes_sent = S * 32 + R * (uint64_t)k * cand; st->bytes_received = R * 32 + S * (uint64_t)k * cand;
   }
+  SETTLE(c, c->sync || st);
   if (c->sync || st) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     if (st) { float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, c->xev[0], c->xev[1])); st->ms = ms; }
   }
   return PT_OK;
@@ -2283,7 +2309,7 @@ int pt_exchange_merge_local(pt_ctx* const* ctxs, int g, const void* const* tgt_x
   }
   if (g == 1) return PT_OK;
   auto restore = [&]() { for (int r = 0; r < g; ++r) ctxs[r]->sync = sync_save[(size_t)r]; };
-  auto all_sync = [&]() -> int { for (int r = 0; r < g; ++r) { pt_ctx* c = ctxs[r]; HIPCHK(c, hipStreamSynchronize(c->stream)); } return PT_OK; };
+  auto all_sync = [&]() -> int { for (int r = 0; r < g; ++r) { int e = settle(ctxs[r], true); if (e) return e; } return PT_OK; };
   auto body = [&]() -> int {
     std::vector<uint32_t> matrix((size_t)g * g, 0), row(64);
     for (int r = 0; r < g; ++r) { int e = xa_count(ctxs[r], A[(size_t)r], slab_bounds); if (e) return e; }

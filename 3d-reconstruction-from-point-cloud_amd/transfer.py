@@ -269,6 +269,10 @@ class PointsTransfer:
         self._adopt_torch_stream()
         self._chk(self._L.pt_blend_dev(self._h, _ptr(idx_dev), _ptr(d2_dev), m, k, mode, _ptr(rgb_out_dev), _ptr(nrm_out_dev)))
 
+    def blend_weighted_dev(self, idx_dev, w_dev, m, k, rgb_out_dev, nrm_out_dev):
+        self._adopt_torch_stream()
+        self._chk(self._L.pt_blend_weighted_dev(self._h, _ptr(idx_dev), _ptr(w_dev), m, k, _ptr(rgb_out_dev), _ptr(nrm_out_dev)))
+
     def pca_normals(self, idx):
         idx = np.ascontiguousarray(idx, np.uint32)
         m, k = idx.shape

@@ -139,11 +139,20 @@ int  pt_ctx_create(pt_ctx** out, const int* device_ids, int n_devices);
 void pt_ctx_destroy(pt_ctx*);
 /* Plumbing: run all work of this context on the caller's hipStream_t (e.g. torch's current stream), so that
  * kernels queue behind whatever produced the device buffers handed in.  NULL = HIP's default stream;
- * pt_set_param(ctx, "own_stream", 1) returns to the context's own (non-blocking) stream. */
+ * pt_set_param(ctx, "own_stream", 1) returns to the context's own (non-blocking) stream.
+ * Switching with work in flight ("sync" 0): when the stream really changes and the context has returned from a call with work still
+ * queued that none of its host waits has covered since (a "sync" 1 call, pt_synchronize), the NEW stream is made to wait for what
+ * the context queued on the OLD one -- one event recorded there, one hipStreamWaitEvent here, no host wait.  So a call after the
+ * switch sees the results and the scratch buffers of the calls before it, and draining the new stream covers both.  This orders the
+ * context's OWN work only: buffers the caller produces on another stream still need the caller's event, and the stream being left
+ * must still exist at the switch.  The context learns that its work is done from its OWN waits only: a caller under "sync" 0 who is
+ * about to destroy the stream the context runs on calls pt_synchronize first (or switches away first) -- a hipStreamSynchronize of
+ * the caller's own leaves the context believing work is queued there, and the next switch fails with PT_ERR_HIP on the dead stream.
+ * Under "sync" 1 every call has drained its stream and a switch costs nothing. */
 int  pt_set_stream(pt_ctx*, void* hip_stream);
 /* Tunables: "k_hint" (the k later queries will use: picks the cell density before a build; default 8), "rho" (points
  * per grid cell, set directly; default 4), "sync" (1 = every call blocks until
- * the GPU is done, default 1; 0 = _dev calls only enqueue), "adaptive" (1 = refine the cell
+ * the GPU is done, default 1; 0 = _dev calls only enqueue -- see "sync" 0 below), "adaptive" (1 = refine the cell
  * size when non-empty cells hold far more than rho points, default; needs one host read-back per build), "tile" (0 = group kernel only, 1 = tile kernel +
  * group kernel for its leftovers with the geometry chosen from the cell density (default), 2 / 3 = force the small /
  * large tile geometry), "guess_min_points" (clouds at least this large lay their grid out from the bounding box of a
@@ -175,6 +184,28 @@ int  pt_set_stream(pt_ctx*, void* hip_stream);
  * from the sample's bound on the points per occupied cell, before the first sort; 0: after it, from the sort's count -- round 3's behaviour),
  * "normals_chunk" (points per chunk of pt_estimate_normals, which bounds its scratch memory; default 8 Mi, at least 1024 -- PT_ERR_ARG
  * below that; small values make a small cloud take many chunks, which is what tests use it for).
+ *
+ * "sync" 0, what it means.  Entry points that take HOST arrays are unchanged: the input may be reused and the outputs are complete when
+ * the call returns (builds and pt_set_attributes* may leave their last kernels queued, behind which every later call of the context
+ * runs).  The _dev entry points return without the trailing wait; their results are ordered on the context's stream (pt_synchronize,
+ * or a consumer on the same stream).  Answers are the same bit for bit under either setting.  What differs:
+ *   - statistics: the device times (ms_build, ms_sort_targets, ms_query, ms_blend, ms_pca, ms_kernel[], and ms_normals unless nrm_out
+ *     is host memory) and n_leftover are refreshed under "sync" 1 only and keep their last values otherwise; tile_variant,
+ *     tile_retry_blocks, query_route and n_wave are valid under both;
+ *   - the tile kernel's leftovers at k <= 16 stay with the 8-lane group kernel, which reads the leftover list and its length on the
+ *     device (PT_ROUTE_TILE | PT_ROUTE_GROUP); under "sync" 1, and at k > 16 under either setting, each gets a wave, sized by a
+ *     read-back of that length (PT_ROUTE_TILE | PT_ROUTE_WAVE);
+ *   - "only enqueue" holds for: pt_blend_dev, pt_blend_weighted_dev, pt_pca_normals_dev, pt_merge_candidates_dev,
+ *     pt_resident_target_ids / _xyz / pt_resident_source_xyz, pt_targets_soa(on_device), and the queries (pt_query_resident,
+ *     pt_query_blend_resident, pt_query_soa(on_device), pt_query_bounded_dev) on a cloud without refined cells or density contrast when
+ *     either the group kernel runs alone ("tile" 0, bounded queries) or the tile kernel runs its large geometry over all blocks with
+ *     k <= 16 ("tile" 3, or "tile" 1 where the cloud's regions exceed the two-per-CU budget; "tile_sparse" not taken);
+ *   - the other query routes still wait ONCE on the host for a count that sizes their next launch: the length of the block list
+ *     ("tile_sparse" 1, or 2 on clouds that leave most of their grid empty and on pt_estimate_normals' chunks); the retry count of a
+ *     two-per-CU geometry ("tile" 2, or "tile" 1 where the regions fit it, k <= 24: at k <= 16 read at once, above shared with the
+ *     next); the leftover list's length at k > 16; the wave lists' lengths on clouds with refined cells, refined cell size, density
+ *     contrast or "wave_force".  pt_slab_need_dev waits for its host slab_bounds, pt_pack_requests_dev for the count it returns,
+ *     pt_estimate_normals once per chunk as its query route does, and every build for its bounding box and occupancy.
  *
  * "max_dist" r (cloud units; r >= 0, +inf = off, the default; NaN or r < 0: PT_ERR_ARG): neighbours farther than r are not returned.
  * R2 = r * r is computed once in double, and a source point is in reach iff d2 <= R2 (d2 the metric above; inclusive, like
