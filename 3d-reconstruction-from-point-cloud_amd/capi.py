@@ -16,6 +16,7 @@ DIST_UNIFORM, DIST_CLUSTERED = 0, 1
 BLEND_MEAN, BLEND_INV_D2 = 0, 1
 MAP_COLOR, MAP_NORMAL = 1, 2
 ORIENT_AXIS, ORIENT_VIEWPOINT = 0, 1
+OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 
 # every symbol include/pt_api.h declares (tests check the .so exports all of them)
@@ -24,7 +25,7 @@ SYMBOLS = [
     "pt_build_aos", "pt_build_soa", "pt_build_soa_indexed", "pt_set_attributes", "pt_set_attributes_range", "pt_set_attributes_local", "pt_build_synth", "pt_rebuild",
     "pt_num_source", "pt_query_aos", "pt_query_soa", "pt_targets_synth", "pt_targets_soa", "pt_targets_aos", "pt_num_targets", "pt_query_resident", "pt_query_blend_resident", "pt_query_resident_host",
     "pt_resident_target_ids", "pt_resident_target_xyz", "pt_resident_source_xyz", "pt_blend", "pt_blend_dev", "pt_blend_weighted", "pt_blend_weighted_dev", "pt_pca_normals",
-    "pt_pca_normals_dev", "pt_estimate_normals", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
+    "pt_pca_normals_dev", "pt_estimate_normals", "pt_remove_outliers", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
     "pt_bake_texture", "pt_bake_maps", "pt_texture_pad", "pt_host_alloc", "pt_host_free", "pt_upload_begin", "pt_upload_range", "pt_upload_end", "pt_stream_query",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_comm_abort", "pt_exchange_merge_dev", "pt_exchange_merge_local", "pt_query_exchange_blend",
 ]
@@ -45,6 +46,7 @@ class Stats(C.Structure):
         ("uniform_probe", C.c_int32), ("dup_leaves", C.c_int32), ("presort_refine", C.c_int32), ("n_sorts", C.c_int32), ("ordered_input", C.c_int32),
         ("tile_variant", C.c_uint32 * 2), ("tile_retry_blocks", C.c_uint32), ("query_route", C.c_uint32),
         ("ms_normals", C.c_double), ("n_normal_chunks", C.c_uint32),
+        ("ms_outliers", C.c_double), ("n_outlier_chunks", C.c_uint32),
     ]
 
 
@@ -54,6 +56,11 @@ ROUTE_TILE, ROUTE_GROUP, ROUTE_GROUP_HIER, ROUTE_WAVE, ROUTE_WAVE_HIER, ROUTE_BL
 
 class ExchangeStats(C.Structure):
     _fields_ = [("crossing", C.c_uint64), ("answered", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64), ("ms", C.c_double)]
+
+
+class OutlierResult(C.Structure):
+    """pt_outlier_result_t"""
+    _fields_ = [("n_before", C.c_uint64), ("n_kept", C.c_uint64), ("n_scored", C.c_uint64), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
 
 
 class PtError(RuntimeError):
@@ -113,6 +120,7 @@ def lib():
         "pt_pca_normals": (i32, [p, p, u64, i32, p]),
         "pt_pca_normals_dev": (i32, [p, p, u64, i32, p]),
         "pt_estimate_normals": (i32, [p, i32, i32, C.POINTER(C.c_double), p, i32]),
+        "pt_remove_outliers": (i32, [p, i32, i32, dbl, i32, p, p, i32, C.POINTER(OutlierResult)]),
         "pt_merge_candidates_dev": (i32, [p, p, p, i32, u64, i32, p, p]),
         "pt_slab_need_dev": (i32, [p, p, i32, p, u64, i32, i32, p, i32, i32, p]),
         "pt_pack_requests_dev": (i32, [p, p, i32, p, u64, i32, i32, p, i32, i32, p, p, p]),

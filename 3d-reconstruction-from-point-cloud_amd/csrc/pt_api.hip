@@ -54,14 +54,14 @@ struct Learned {
 };
 
 // Words of the pinned read-back buffers.  `counter` (device) and `h_counter` (host): 16 32-bit words, a count is read back into the host
-// word of the same number unless the entry says otherwise.  `h_bbox`: 10 64-bit words.
+// word of the same number unless the entry says otherwise.  `h_bbox`: 14 64-bit words.
 enum Slot : int {
   RB_SLAB_N = 0,       // 1 word: points a generated slab keeps (pt_build_synth, pt_targets_synth)
   RB_ASCENDING = 1,    // 1 word: nonzero when a slab's gidx does not ascend (pt_build_soa_indexed)
   RB_DEDUP = 2,        // 2 words: leaves, records (rebuild, dedup_leaves)
   RB_TODO = 4,         // 1 word: targets the tile kernel left over (run_query)
   RB_RETRY = 5,        // 1 word: blocks for the tile kernel's second chance (run_query)
-  RB_COUNT = 6,        // 1 word: packets of pt_pack_requests_dev / targets in reach of a chunk (pt_stream_query)
+  RB_COUNT = 6,        // 1 word: packets of pt_pack_requests_dev / targets in reach of a chunk (pt_stream_query) / points pt_remove_outliers keeps
   RB_TLIST = 7,        // 1 word: blocks that hold targets (run_query, sparse tile launch)
   RB_OCC = 8,          // 2 words: sum, max (rebuild, occupied cells and the fullest one)
   RB_NODES = 10,       // 1 word: nodes of the refinement so far (rebuild)
@@ -74,7 +74,8 @@ enum Slot : int {
   BB_BOX = 0,          // h_bbox, 6 words: the encoded bounding box {min xyz, max xyz} (source_bbox, rebuild's verified box)
   BB_CHI2 = 6, BB_DOF = 7, BB_OCC = 8, BB_SAME = 9,     // h_bbox, 1 word each, from the uniform probe (rebuild): chi-square sum (x 1024), blocks it
                                                         // is over, occupied cells (x 16), sample points in their wave's first block
-  BB_WORDS = 10,
+  BB_OUTLIER = 10,     // h_bbox, 4 words read as doubles: finite scores, mean, stddev, threshold (pt_remove_outliers)
+  BB_WORDS = 14,
 };
 
 // The branch on the coordinate type: f(x, Rec{}) with `xyz` typed as float (PT_F32) or double, const as given, Rec its record type.  by_coords
@@ -127,8 +128,9 @@ struct pt_ctx {
   float e_src = 0.f;           // fp64 clouds: largest rounding error of a source coordinate stored as fp32
   DevBuf posattr;              // fp32 clouds: {position, attributes} by original index for the PCA pass, built on first use
   DevBuf pos16;                // fp32 / fp16 clouds: {x, y, z, 0} by original index, written by every pt_estimate_normals call
-  uint64_t normals_chunk = 8u << 20;      // "normals_chunk": points per chunk of pt_estimate_normals
-  hipEvent_t nev[2] = {nullptr, nullptr}; // ... and its timing (run_query uses ev[0..2] itself)
+  uint64_t normals_chunk = 8u << 20;      // "normals_chunk": points per chunk of the self-query passes (pt_estimate_normals, pt_remove_outliers)
+  hipEvent_t nev[2] = {nullptr, nullptr}; // ... and their timing (run_query uses ev[0..2] itself)
+  DevBuf outl;                   // pt_remove_outliers: scores (8 n), kept indices (4 n), mask (n), tile offsets, reduction partials, result words
   bool posattr_valid = false;
   Learned learned;
   bool slab() const { return ids != IdMode::whole; }
@@ -1147,7 +1149,7 @@ void pt_ctx_destroy(pt_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf* all[] = {&c->in_xyz, &c->in_gidx, &c->attr, &c->rec, &c->rec_tmp, &c->cell_start, &c->stb_mem, &c->t_xyz, &c->t_gidx, &c->trec,
                    &c->trec_tmp, &c->x_xyz, &c->ttb_mem, &c->bbox6, &c->counter, &c->q_idx, &c->q_d2, &c->b_rgb, &c->b_nrm, &c->aos_stage, &c->misc, &c->bounds, &c->todo, &c->posattr, &c->retry, &c->rec32, &c->up_rgb, &c->up_nrm, &c->x_bounds, &c->x_counts, &c->x_matrix, &c->x_off, &c->x_req, &c->x_row, &c->x_rreq,
-                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd, &c->pos16};
+                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd, &c->pos16, &c->outl};
   for (DevBuf* b : all) release(c, *b);
   if (c->h_bbox) (void)hipHostFree(c->h_bbox);
   if (c->h_counter) (void)hipHostFree(c->h_counter);
@@ -1178,7 +1180,7 @@ int pt_set_param(pt_ctx* c, const char* name, double value) {
     c->cap2 = value * value;
     return PT_OK;
   }
-  if (!strcmp(name, "normals_chunk")) {       // (a setting of pt_estimate_normals: no build depends on it)
+  if (!strcmp(name, "normals_chunk")) {       // (a setting of pt_estimate_normals / pt_remove_outliers: no build depends on it)
     if (!(value >= 1024.0 && value <= 4294967295.0)) return fail(c, PT_ERR_ARG, "normals_chunk must be in [1024, 2^32), got %g", value);
     c->normals_chunk = (uint64_t)value;
     return PT_OK;
@@ -1716,6 +1718,110 @@ int pt_estimate_normals(pt_ctx* c, int k, int orient, const double* ref, float* 
       HIPCHK(c, hipMemcpyAsync(nrm_out + 3 * a, c->b_nrm.p, (size_t)m * 12, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+  }
+  return PT_OK;
+}
+
+// outliers of the resident cloud itself (include/pt_api.h): the self-query of pt_estimate_normals, chunk by chunk, now with the d2 rows ->
+// one score per point -> (statistical) two deterministic reductions -> the keep mask -> (apply) the mask as an ordered list of kept
+// indices, coordinates and attribute records gathered through the sort's own record buffers, and the grid built over what is left
+int pt_remove_outliers(pt_ctx* c, int mode, int k, double param, int apply, uint8_t* keep_out, double* score_out, int out_on_device,
+                       pt_outlier_result_t* result) {
+  if (!c) return PT_ERR_ARG;
+  if (result) *result = pt_outlier_result_t{};
+  if (!c->built) return fail(c, PT_ERR_STATE, "pt_remove_outliers before a build");
+  if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "pt_remove_outliers needs the whole cloud resident (not a slab)");
+  if (mode != PT_OUTLIER_STATISTICAL && mode != PT_OUTLIER_RADIUS) return fail(c, PT_ERR_ARG, "unknown outlier mode %d", mode);
+  if (k < 2 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [2, %d]", k, PT_MAX_K);
+  const bool radius = mode == PT_OUTLIER_RADIUS;
+  if (radius ? !(std::isfinite(param) && param > 0.0) : !(std::isfinite(param) && param >= 0.0))
+    return fail(c, PT_ERR_ARG, radius ? "the radius must be finite and > 0, got %g" : "alpha must be finite and >= 0, got %g", param);
+  c->st.ms_outliers = 0.0; c->st.n_outlier_chunks = 0;
+  const uint64_t n = c->n;
+  if (!n) return PT_OK;
+  if (c->has_attr && c->n_total != n) return fail(c, PT_ERR_STATE, "the attribute table holds %llu records, the cloud %llu points", (unsigned long long)c->n_total, (unsigned long long)n);
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t chunk = std::min<uint64_t>(c->normals_chunk, n);
+  // one allocation: scores | kept indices | mask (padded to whole words) | tile offsets of the two mark lists and their scan scratch |
+  // the reductions' partial sums and counts | the four result words
+  const uint32_t mtiles = pt_mark_tiles((uint32_t)n), nparts = pt_outlier_parts((uint32_t)n);
+  const size_t mask_bytes = ((size_t)n + 15) & ~(size_t)15;
+  RES(c, c->outl, n * 8 + n * 4 + 16 + mask_bytes + ((size_t)mtiles + 4) * 3 * sizeof(uint32_t) + 16 + (size_t)nparts * 12 + 16 + 64);
+  double* score = (double*)c->outl.p;
+  double* part_sum = score + n;
+  double* res = part_sum + nparts;
+  uint32_t* map = (uint32_t*)(res + 4);
+  uint32_t* off1 = map + n;
+  uint32_t* off2 = off1 + mtiles + 4;
+  uint32_t* scan = off2 + mtiles + 4;
+  uint32_t* part_cnt = scan + mtiles + 4;
+  uint8_t* keep = (uint8_t*)(((uintptr_t)(part_cnt + nparts) + 15) & ~(uintptr_t)15);
+  RES(c, c->q_idx, chunk * (uint64_t)k * sizeof(uint32_t));
+  RES(c, c->q_d2, chunk * (uint64_t)k * sizeof(double));
+  HIPCHK(c, hipEventRecord(c->nev[0], c->stream));
+  // radius mode searches under reach min(r, max_dist) for the length of the call: one more cap on the lists, nothing else changes
+  const double cap2_saved = c->cap2;
+  if (radius) c->cap2 = std::min(c->cap2, param * param);
+  double ms_copy = 0.0, ms_search = 0.0;
+  uint32_t nchunks = 0;
+  int qr = PT_OK;
+  for (uint64_t a = 0; a < n && qr == PT_OK; a += chunk, ++nchunks) {
+    const uint32_t first = (uint32_t)a, m = (uint32_t)std::min<uint64_t>(chunk, n - a);
+    qr = run_query(c, c->in_xyz.p, c->src_type, m, k, nullptr, (uint32_t*)c->q_idx.p, (double*)c->q_d2.p, nullptr, &first);
+    if (qr != PT_OK) break;
+    ms_copy += c->st.ms_sort_targets; ms_search += c->st.ms_query;
+    if (c->src_type == PT_F64) pt_launch_outlier_score((const double*)c->q_d2.p, (const uint32_t*)c->q_idx.p, m, k, (const RecD*)c->rec.p + a, radius ? 1 : 0, score, c->stream);
+    else pt_launch_outlier_score((const double*)c->q_d2.p, (const uint32_t*)c->q_idx.p, m, k, (const RecF*)c->rec.p + a, radius ? 1 : 0, score, c->stream);
+  }
+  c->cap2 = cap2_saved;
+  if (qr != PT_OK) return qr;
+  c->st.n_outlier_chunks = nchunks;
+  if (!radius) pt_launch_outlier_stats(score, (uint32_t)n, param, part_sum, part_cnt, res, c->stream);
+  pt_launch_outlier_mask(score, (uint32_t)n, res, radius ? 1 : 0, (double)(k - 1), keep, c->stream);
+  pt_launch_mark_count(keep, (uint32_t)n, off1, off2, scan, c->stream);
+  HIPCHK(c, hipGetLastError());
+  // the call's one host wait of its own: the reduction's result and the number of points kept, which sizes the compaction
+  if (!radius) HIPCHK(c, hipMemcpyAsync(c->h_bbox + BB_OUTLIER, res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_COUNT, off1 + mtiles, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t n_kept = c->h_counter[RB_COUNT];
+  if (result) {
+    result->n_before = n; result->n_kept = n_kept;
+    if (radius) { result->n_scored = n; result->threshold = (double)(k - 1); }
+    else {
+      double r4[4];
+      memcpy(r4, c->h_bbox + BB_OUTLIER, sizeof r4);
+      result->n_scored = (uint64_t)r4[0]; result->mean = r4[1]; result->stddev = r4[2]; result->threshold = r4[3];
+    }
+  }
+  const hipMemcpyKind out_kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, keep, n, out_kind, c->stream));
+  if (score_out) HIPCHK(c, hipMemcpyAsync(score_out, score, n * sizeof(double), out_kind, c->stream));
+  if ((keep_out || score_out) && !out_on_device) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (apply && n_kept == 0) return fail(c, PT_ERR_ARG, "pt_remove_outliers would remove every point (the cloud is unchanged)");
+  const bool compact = apply && n_kept < n;
+  if (compact) {
+    // the kept original indices in order = the new -> old map; the planes and the records are gathered into the sort's record buffers
+    // (the rebuild overwrites both) and copied back to the front of their own buffers
+    const uint32_t nk = (uint32_t)n_kept;
+    pt_launch_mark_write(keep, (uint32_t)n, off1, off2, map, map, c->stream);
+    const size_t es = c->in_half ? sizeof(__half) : tsize(c->src_type);
+    pt_launch_gather(c->in_xyz.p, n, es, map, nk, 3, c->rec_tmp.p, c->stream);
+    if (c->has_attr) pt_launch_gather(c->attr.p, 0, sizeof(Attr), map, nk, 1, c->rec.p, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->in_xyz.p, c->rec_tmp.p, (size_t)nk * 3 * es, hipMemcpyDeviceToDevice, c->stream));
+    if (c->has_attr) HIPCHK(c, hipMemcpyAsync(c->attr.p, c->rec.p, (size_t)nk * sizeof(Attr), hipMemcpyDeviceToDevice, c->stream));
+    adopt_cloud(c, c->src_type, n_kept, n_kept, IdMode::whole, c->in_half, c->has_attr);     // a new whole cloud: everything derived is invalid, nothing learned carries over
+    c->rec32_valid = false;
+    { int r = rebuild(c); if (r != PT_OK) return r; }
+  }
+  HIPCHK(c, hipEventRecord(c->nev[1], c->stream));
+  SETTLE(c, c->sync != 0);
+  if (c->sync) {
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->nev[0], c->nev[1]));
+    c->st.ms_outliers = ms;
+    c->st.ms_sort_targets = ms_copy; c->st.ms_query = ms_search;      // (sums over the chunks, as pt_estimate_normals reports them)
   }
   return PT_OK;
 }

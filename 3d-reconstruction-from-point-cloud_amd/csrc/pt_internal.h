@@ -1,5 +1,5 @@
 // pt_internal.h -- host-side launch interface between the C-ABI glue (pt_api.hip) and the kernel
-// translation units (pt_grid.hip, pt_knn_group.hip / pt_knn_wave.hip / pt_knn_tile.hip, pt_query.hip, pt_attr.hip, ...).  Everything takes the stream to launch on;
+// translation units (pt_grid.hip, pt_knn_group.hip / pt_knn_wave.hip / pt_knn_tile.hip, pt_query.hip, pt_attr.hip, pt_outlier.hip, ...).  Everything takes the stream to launch on;
 // nothing here allocates or synchronises.
 #pragma once
 #include "pt_common.h"
@@ -198,6 +198,22 @@ void pt_launch_self_pca(const uint32_t* idx, uint32_t m, int k, const RecD* rec,
                         float* nrm_out, hipStream_t s);
 // out[i][3] = the normals of the attribute records [first, first + count)
 void pt_launch_attr_normals(const Attr* attr, uint32_t first, uint32_t count, float* out, hipStream_t s);
+
+// ---- pt_outlier.hip: outlier removal on the resident cloud (pt_remove_outliers) -----------------------------------
+// One score per row of a chunk's own lists d2[m][k] / idx[m][k]: row t belongs to the source record rec[t] (rec = the sorted records + a)
+// and its score goes to score[rec[t].id].  radius_mode 0: mean distance to the other entries that name a point (+inf with fewer than
+// two entries); 1: the number of such other entries.  A row is summed left to right by one thread: the order depends on k alone
+template <class Rec>
+void pt_launch_outlier_score(const double* d2, const uint32_t* idx, uint32_t m, int k, const Rec* rec, int radius_mode, double* score, hipStream_t s);
+// The two reductions over score[n] by original index (finite scores only), four launches: res[0] = their number, res[1] = mean,
+// res[2] = population stddev (second pass over the table), res[3] = mean + alpha * stddev.  part_sum / part_cnt: pt_outlier_parts(n)
+// entries each -- a grid fixed by n alone, partials added in index order, no floating-point atomics
+uint32_t pt_outlier_parts(uint32_t n);
+void pt_launch_outlier_stats(const double* score, uint32_t n, double alpha, double* part_sum, uint32_t* part_cnt, double* res, hipStream_t s);
+// keep[i] = score[i] <= res[3] (radius_mode 0) or score[i] == full (1); keep holds (n + 3) & ~3 bytes, 4-byte aligned
+void pt_launch_outlier_mask(const double* score, uint32_t n, const double* res, int radius_mode, double full, uint8_t* keep, hipStream_t s);
+// out[p * nk + j] = in[p * in_stride + map[j]] for p < planes, elements of 2, 4, 8 or 16 bytes (map: the kept original indices, ascending)
+void pt_launch_gather(const void* in, size_t in_stride, size_t elem_bytes, const uint32_t* map, uint32_t nk, int planes, void* out, hipStream_t s);
 
 // ---- pt_bake.hip ------------------------------------------------------------------------------
 // per-face texture bake (reference src/pointsTransfer.cpp:466-581, :66-107): every covered pixel of the R x R atlas does an

@@ -29,6 +29,13 @@
 //                    (pt_estimate_normals, K in 3..32) in place of the ones the file carries: the blended vertex normals, transfer.ply
 //                    and --normal-map then use them.  --viewpoint X Y Z orients them towards that point (default: +z).  Not with
 //                    --synthetic, not with --gpus N > 1 (the pass needs the whole cloud on one GPU; --gpus 1 runs unsharded): exit 2
+//   --remove-isolated MIN R  after the build, drop every cloud point with fewer than MIN other points within R (pt_remove_outliers,
+//                    radius filter; MIN in 1..31, R > 0), and
+//   --remove-outliers K ALPHA  drop every point whose mean distance to its K - 1 nearest other points exceeds the cloud's mean + ALPHA
+//                    standard deviations of that score (statistical filter; K in 2..32, ALPHA >= 0).  Both may be given: the radius filter
+//                    runs first; both run before --estimate-normals, and the search, transfer.ply, the texture and the normal map see the
+//                    filtered cloud.  stderr reports kept / removed / threshold / ms per filter.  Not with --synthetic, not with
+//                    --gpus N > 1 (a slab does not hold its points' neighbours; --gpus 1 runs unsharded): exit 2
 // There is no CPU path: without a usable GPU the tool reports the error and exits non-zero.
 #include <chrono>
 #include <cmath>
@@ -125,6 +132,9 @@ int main(int argc, char** argv) {
   int est_k = 0;                                   // --estimate-normals K (0: off)
   bool est_given = false, vp_given = false, vp_ok = true;
   double viewpoint[3] = {0.0, 0.0, 0.0};           // --viewpoint X Y Z
+  int sor_k = 0, rad_min = 0;                      // --remove-outliers K ALPHA, --remove-isolated MIN R
+  double sor_alpha = 0.0, rad_r = 0.0;
+  bool sor_given = false, sor_ok = true, rad_given = false, rad_ok = true;
   std::string rendezvous;
   // --synthetic N M SEED [--clustered] [--xyz f32|f16|f64]: SURVEY.md Appendix C's generator instead of the two files (the positional
   // arguments are ignored): the BASELINE configurations run through this binary without a cloud on disk -- no mesh, so no texture
@@ -171,6 +181,17 @@ int main(int argc, char** argv) {
         vp_ok = vp_ok && *v && end && !*end && std::isfinite(viewpoint[q]);
       }
     }
+    else if (a == "--remove-outliers" || a == "--remove-isolated") {
+      const bool sor = a == "--remove-outliers";
+      const char* v1 = val();
+      const char* v2 = val();
+      char *e1 = nullptr, *e2 = nullptr;
+      const long cnt = std::strtol(v1, &e1, 10);
+      const double x = std::strtod(v2, &e2);
+      const bool parsed = *v1 && e1 && !*e1 && *v2 && e2 && !*e2 && std::isfinite(x);
+      if (sor) { sor_given = true; sor_k = (int)std::max(-1L, std::min(cnt, 1000L)); sor_alpha = x; sor_ok = parsed && cnt >= 2 && cnt <= PT_MAX_K && x >= 0.0; }
+      else { rad_given = true; rad_min = (int)std::max(-1L, std::min(cnt, 1000L)); rad_r = x; rad_ok = parsed && cnt >= 1 && cnt <= PT_MAX_K - 1 && x > 0.0; }
+    }
     else { std::cerr << "unknown option " << a << std::endl; return 2; }
     for (int j = i_before; j <= i; ++j) passthrough.push_back(argv[j]);
   }
@@ -183,7 +204,12 @@ int main(int argc, char** argv) {
   if (vp_given && !vp_ok) { std::cerr << "--viewpoint needs three finite numbers" << std::endl; return 2; }
   if (est_given && synthetic) { std::cerr << "--estimate-normals / --viewpoint: not with --synthetic (the generated cloud has normals)" << std::endl; return 2; }
   if (est_given && (gpus > 1 || rank >= 0 || finalize)) { std::cerr << "--estimate-normals / --viewpoint: not with --gpus N > 1 (the pass needs the whole cloud on one GPU)" << std::endl; return 2; }
-  if (est_given && gpus == 1) gpus = 0;            // (one GPU: the unsharded path, which holds the whole cloud)
+  if (sor_given && !sor_ok) { std::cerr << "--remove-outliers needs K in [2, " << PT_MAX_K << "] and a finite ALPHA >= 0" << std::endl; return 2; }
+  if (rad_given && !rad_ok) { std::cerr << "--remove-isolated needs MIN in [1, " << PT_MAX_K - 1 << "] and a finite R > 0" << std::endl; return 2; }
+  const char* filter_flags = sor_given && rad_given ? "--remove-outliers / --remove-isolated" : (sor_given ? "--remove-outliers" : "--remove-isolated");
+  if ((sor_given || rad_given) && synthetic) { std::cerr << filter_flags << ": not with --synthetic (the generated cloud has no strays)" << std::endl; return 2; }
+  if ((sor_given || rad_given) && (gpus > 1 || rank >= 0 || finalize)) { std::cerr << filter_flags << ": not with --gpus N > 1 (a slab does not hold its points' neighbours)" << std::endl; return 2; }
+  if ((est_given || sor_given || rad_given) && gpus == 1) gpus = 0;            // (one GPU: the unsharded path, which holds the whole cloud)
   const bool capped = max_dist < INFINITY;
   // vertices whose list came back empty under the cap (reported on stderr and in --json; the stdout lines stay the reference's)
   auto count_empty = [&](const std::vector<uint32_t>& ids, size_t rows) {
@@ -321,6 +347,17 @@ int main(int argc, char** argv) {
   if (rc == PT_OK) rc = pt_upload_end(ctx);
   free_pinned();
   if (rc != PT_OK) { std::cerr << "pointsTransfer: build failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+  for (int f = 0; f < 2; ++f) {                    // the filters, radius first (inside the build's line, like the normals pass)
+    if (!(f == 0 ? rad_given : sor_given)) continue;
+    pt_outlier_result_t orr;
+    rc = f == 0 ? pt_remove_outliers(ctx, PT_OUTLIER_RADIUS, rad_min + 1, rad_r, 1, nullptr, nullptr, 0, &orr)
+                : pt_remove_outliers(ctx, PT_OUTLIER_STATISTICAL, sor_k, sor_alpha, 1, nullptr, nullptr, 0, &orr);
+    if (rc != PT_OK) { std::cerr << "pointsTransfer: " << (f == 0 ? "--remove-isolated" : "--remove-outliers") << " failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+    pt_stats_t so;
+    if (pt_stats(ctx, &so) == PT_OK)
+      std::cerr << "[pt_hip] " << (f == 0 ? "--remove-isolated" : "--remove-outliers") << ": kept " << orr.n_kept << ", removed " << orr.n_before - orr.n_kept << " of " << orr.n_before
+                << " points, threshold " << orr.threshold << ", " << so.ms_outliers << " ms (device time)" << std::endl;
+  }
   if (est_given) {                                 // (inside the build's line: stdout keeps the reference's set of lines)
     rc = pt_estimate_normals(ctx, est_k, vp_given ? PT_ORIENT_VIEWPOINT : PT_ORIENT_AXIS, vp_given ? viewpoint : nullptr, nullptr, 0);
     if (rc != PT_OK) { std::cerr << "pointsTransfer: normal estimation failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }

@@ -311,6 +311,36 @@ class PointsTransfer:
         self._adopt_torch_stream()
         self._chk(self._L.pt_estimate_normals(self._h, k, mode, ref, _ptr(nrm_out_dev), 1))
 
+    @staticmethod
+    def _outlier_mode(k, alpha, radius, min_neighbors):
+        if (radius is None) != (min_neighbors is None):
+            raise ValueError("remove_outliers: give radius and min_neighbors together (the radius filter), or neither (the statistical one)")
+        if radius is None:
+            return capi.OUTLIER_STATISTICAL, int(k), float(alpha)
+        return capi.OUTLIER_RADIUS, int(min_neighbors) + 1, float(radius)
+
+    def remove_outliers(self, k=16, alpha=2.0, *, radius=None, min_neighbors=None, apply=True):
+        """Take stray points out of the resident cloud (pt_remove_outliers).  Statistical filter (default): a point is kept when the mean
+        distance to its k - 1 nearest other points is at most mean + alpha * stddev of that score over the cloud.  Radius filter
+        (radius and min_neighbors given together): kept when at least min_neighbors other points lie within radius.  Returns
+        (keep bool (n,), scores float64 (n,), info dict), all by original index; with apply=True the resident cloud (and its attribute
+        table) becomes the kept points in their original order -- np.cumsum(keep) - 1 maps old indices to new ones."""
+        mode, kk, param = self._outlier_mode(k, alpha, radius, min_neighbors)
+        n = self.num_source
+        keep = np.zeros(n, np.uint8)
+        scores = np.zeros(n, np.float64)
+        res = capi.OutlierResult()
+        self._chk(self._L.pt_remove_outliers(self._h, mode, kk, param, 1 if apply else 0, _ptr(keep), _ptr(scores), 0, C.byref(res)))
+        return keep.astype(bool), scores, {f[0]: getattr(res, f[0]) for f in res._fields_}
+
+    def remove_outliers_dev(self, keep_dev, scores_dev, k=16, alpha=2.0, *, radius=None, min_neighbors=None, apply=True):
+        """The same with the uint8 (n,) mask and the float64 (n,) scores written to device buffers (either may be None); returns info."""
+        mode, kk, param = self._outlier_mode(k, alpha, radius, min_neighbors)
+        self._adopt_torch_stream()
+        res = capi.OutlierResult()
+        self._chk(self._L.pt_remove_outliers(self._h, mode, kk, param, 1 if apply else 0, _ptr(keep_dev), _ptr(scores_dev), 1, C.byref(res)))
+        return {f[0]: getattr(res, f[0]) for f in res._fields_}
+
     # -- native slab exchange over RCCL (SURVEY.md 8e) ---------------------------------------------
     @staticmethod
     def comm_unique_id():

@@ -122,6 +122,9 @@ typedef struct pt_stats_t {
                              * turns out empty -- its length stays on the device) */
   double ms_normals;        /* pt_estimate_normals: device time of the last call, every chunk's copy, search and PCA included (HIP events) */
   uint32_t n_normal_chunks; /* ... and the number of chunks it walked the cloud in */
+  double ms_outliers;       /* pt_remove_outliers: device time of the last call -- every chunk's search and scores, the reductions, the mask, and under
+                             * `apply` the compaction and the rebuild (HIP events) */
+  uint32_t n_outlier_chunks; /* ... and the number of chunks it walked the cloud in */
 } pt_stats_t;
 enum {
   PT_ROUTE_TILE = 1,        /* the LDS tile kernel */
@@ -182,8 +185,8 @@ int  pt_set_stream(pt_ctx*, void* hip_stream);
  * global indices, or a slab pt_build_synth generates -- keeps positions in its records and its own attribute records only; see
  * pt_set_attributes_local), "presort_refine" (1, default: the first build of a big cloud the sample finds non-uniform refines its cell size
  * from the sample's bound on the points per occupied cell, before the first sort; 0: after it, from the sort's count -- round 3's behaviour),
- * "normals_chunk" (points per chunk of pt_estimate_normals, which bounds its scratch memory; default 8 Mi, at least 1024 -- PT_ERR_ARG
- * below that; small values make a small cloud take many chunks, which is what tests use it for).
+ * "normals_chunk" (points per chunk of the self-query passes: pt_estimate_normals, pt_remove_outliers -- it bounds their scratch memory;
+ * default 8 Mi, at least 1024 -- PT_ERR_ARG below that; small values make a small cloud take many chunks, which is what tests use it for).
  *
  * "sync" 0, what it means.  Entry points that take HOST arrays are unchanged: the input may be reused and the outputs are complete when
  * the call returns (builds and pt_set_attributes* may leave their last kernels queued, behind which every later call of the context
@@ -205,7 +208,11 @@ int  pt_set_stream(pt_ctx*, void* hip_stream);
  *     two-per-CU geometry ("tile" 2, or "tile" 1 where the regions fit it, k <= 24: at k <= 16 read at once, above shared with the
  *     next); the leftover list's length at k > 16; the wave lists' lengths on clouds with refined cells, refined cell size, density
  *     contrast or "wave_force".  pt_slab_need_dev waits for its host slab_bounds, pt_pack_requests_dev for the count it returns,
- *     pt_estimate_normals once per chunk as its query route does, and every build for its bounding box and occupancy.
+ *     pt_estimate_normals once per chunk as its query route does, and every build for its bounding box and occupancy;
+ *   - pt_remove_outliers waits on the host wherever its query route waits, as pt_estimate_normals does, and once more for the reduction's
+ *     result and n_kept, which size the compaction (under `apply` the rebuild waits as every build does); device outputs (keep_out,
+ *     score_out with out_on_device) are ordered on the context's stream;
+ *   - ms_outliers is refreshed under "sync" 1 only.
  *
  * "max_dist" r (cloud units; r >= 0, +inf = off, the default; NaN or r < 0: PT_ERR_ARG): neighbours farther than r are not returned.
  * R2 = r * r is computed once in double, and a source point is in reach iff d2 <= R2 (d2 the metric above; inclusive, like
@@ -349,6 +356,58 @@ int  pt_pca_normals_dev(pt_ctx*, const uint32_t* idx_dev, uint64_t m, int k, flo
  * pt_stats_t: ms_normals, n_normal_chunks. */
 typedef enum { PT_ORIENT_AXIS = 0, PT_ORIENT_VIEWPOINT = 1 } pt_orient_mode;
 int  pt_estimate_normals(pt_ctx*, int k, int orient, const double ref3_or_null[3], float* nrm_out_or_null, int out_on_device);
+
+/* pt_remove_outliers: take stray points (flyers between surfaces, returns through windows, sky points) out of the resident cloud, on the
+ * device: no [n][k] matrix crosses PCIe and nothing is uploaded again.  Needs a built, whole cloud: PT_ERR_STATE before a build (or when
+ * an attribute table is resident whose n_total differs from n), PT_ERR_UNSUPPORTED on a slab context (pt_build_soa_indexed, a slab of
+ * pt_build_synth, "local_ids") -- a slab does not hold its points' neighbours.  fp32, fp16 and fp64 clouds alike.
+ * The list of point i is pt_estimate_normals' list: what a pt_query_* call with this k returns for a target at i's own position against
+ * the resident cloud -- (d2, index) order, capped under "max_dist"; entry 0 is i itself or a lower-indexed duplicate, at d2 = 0.  c is the
+ * number of its entries that name a point.
+ *   PT_OUTLIER_STATISTICAL  k in [2, PT_MAX_K], param = alpha (finite, >= 0).  Score s_i = (sum over j = 1 .. c-1 of sqrt(d2_j)) / (c - 1) in
+ *     double when c >= 2, added in list order from j = 1 up (an order that depends on nothing but k); +inf when c <= 1 -- a point alone
+ *     under the cap, always removed.  Over the n_f points with finite scores: mean = sum(s) / n_f, stddev = sqrt(sum((s - mean)^2) / n_f)
+ *     -- the population value, from a second pass over the scores, not from sum(s^2) -- and threshold T = mean + alpha * stddev (n_f = 0:
+ *     all three are 0).  Point i is kept iff s_i <= T.  Both sums run over the score table BY ORIGINAL INDEX after the last chunk:
+ *     workgroup w adds the finite scores of indices [4096 w, 4096 (w + 1)) (thread t those at t, t + 256, ... in that order, then a tree
+ *     over the 256 threads) and one workgroup adds the partials the same way -- a grid fixed by n alone, no floating-point atomics.  So
+ *     mean, stddev, T and the mask are bit-identical from run to run, for every "normals_chunk", every search route and every device.
+ *   PT_OUTLIER_RADIUS  k = m + 1 in [2, PT_MAX_K], m the number of OTHER points required; param = r (finite, > 0).  For the length of the
+ *     call the lists are searched under reach min(r, max_dist): R2 = r * r computed once in double, d2 <= R2 inclusive, exactly like
+ *     "max_dist", which is unchanged when the call returns, whether it succeeds or fails.  Score = c - 1 as a double; i is kept iff
+ *     c == k.  No floating-point sum is involved: the mask is exact.
+ * Outputs: keep_out uint8[n_before] (1 = kept) and score_out double[n_before], both by original index, in host or device memory according to
+ * out_on_device; either may be NULL.  result (may be NULL) is host memory: n_before, n_kept, n_scored (STATISTICAL: n_f; RADIUS: n_before)
+ * and mean / stddev / threshold (RADIUS: 0, 0, k - 1).  n = 0: PT_OK, a zero result, nothing written.
+ * apply = 0: the resident cloud -- source records, attribute table, resident targets -- is untouched, and so is what the context learned
+ *   for its next build.
+ * apply = 1, 0 < n_kept < n_before: the resident cloud becomes the kept points in their original relative order; the new index of a kept
+ *   point is the number of kept points with a smaller original index (the cumulative sum of keep_out maps old to new).  The planar
+ *   coordinates are compacted in the width they are held in (fp16, fp32, fp64), the attribute table likewise when one is resident,
+ *   everything derived from the old cloud is dropped, and the grid is built over the result as over a new cloud.  Afterwards EVERY entry
+ *   point behaves exactly as on a fresh context on which pt_build_soa (+ attributes) was called with the kept subset, results bit for
+ *   bit: pt_num_source, every query, the blends, pt_estimate_normals, pt_pca_normals, pt_bake_maps, pt_resident_source_xyz.  Resident
+ *   targets are left as they were.
+ * apply = 1, n_kept = n_before: mask and scores are delivered, nothing is rebuilt, PT_OK.
+ * apply = 1, n_kept = 0: PT_ERR_ARG ("would remove every point") after mask, scores and result have been delivered; the cloud is unchanged.
+ * PT_ERR_ARG also for an unknown mode, k out of range, a param that is not finite or out of range.
+ * Memory: the lists never exist for the whole cloud (chunks of c = "normals_chunk" points, as pt_estimate_normals).  Scratch:
+ *   c * (12 k + 2 r + 9) bytes (index and d2 rows, two target record buffers of r = 16 or 32 bytes, leftover list, wave marks), 8 c more
+ *   under a cap or in RADIUS mode, 20 bytes per 512-cell grid block, and 13 n + n / 100 bytes that stay with the context until it is
+ *   destroyed: scores (8 n), the kept indices (4 n), the mask (n), and the mask's tile offsets (12 bytes per 2048 points) and the
+ *   reductions' partials (12 bytes per 4096 points).
+ *   The compaction gathers into the sort's own record buffers, which the rebuild overwrites anyway: no second copy of the cloud.
+ * pt_stats_t: ms_outliers, n_outlier_chunks; the statistics of "the last query" are those of the last chunk, with ms_sort_targets /
+ * ms_query summed over the chunks ("sync" 1). */
+typedef enum { PT_OUTLIER_STATISTICAL = 0, PT_OUTLIER_RADIUS = 1 } pt_outlier_mode;
+typedef struct pt_outlier_result_t {
+  uint64_t n_before, n_kept;
+  uint64_t n_scored;            /* STATISTICAL: points with a finite score (what mean / stddev run over); RADIUS: n_before */
+  double mean, stddev, threshold;   /* STATISTICAL; RADIUS: 0, 0, k - 1 */
+} pt_outlier_result_t;
+int  pt_remove_outliers(pt_ctx*, int mode, int k, double param, int apply,
+                        uint8_t* keep_out_or_null, double* score_out_or_null, int out_on_device,
+                        pt_outlier_result_t* result_or_null);
 
 /* ---- multi-GPU merge ---------------------------------------------------------- */
 /* G-way merge of candidate lists under (d2, idx): lists are [g][m][k] device arrays. */
