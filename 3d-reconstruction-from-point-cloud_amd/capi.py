@@ -25,7 +25,7 @@ SYMBOLS = [
     "pt_build_aos", "pt_build_soa", "pt_build_soa_indexed", "pt_set_attributes", "pt_set_attributes_range", "pt_set_attributes_local", "pt_build_synth", "pt_rebuild",
     "pt_num_source", "pt_query_aos", "pt_query_soa", "pt_targets_synth", "pt_targets_soa", "pt_targets_aos", "pt_num_targets", "pt_query_resident", "pt_query_blend_resident", "pt_query_resident_host",
     "pt_resident_target_ids", "pt_resident_target_xyz", "pt_resident_source_xyz", "pt_blend", "pt_blend_dev", "pt_blend_weighted", "pt_blend_weighted_dev", "pt_pca_normals",
-    "pt_pca_normals_dev", "pt_estimate_normals", "pt_remove_outliers", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
+    "pt_pca_normals_dev", "pt_estimate_normals", "pt_remove_outliers", "pt_voxel_downsample", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
     "pt_bake_texture", "pt_bake_maps", "pt_texture_pad", "pt_host_alloc", "pt_host_free", "pt_upload_begin", "pt_upload_range", "pt_upload_end", "pt_stream_query",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_comm_abort", "pt_exchange_merge_dev", "pt_exchange_merge_local", "pt_query_exchange_blend",
 ]
@@ -47,6 +47,7 @@ class Stats(C.Structure):
         ("tile_variant", C.c_uint32 * 2), ("tile_retry_blocks", C.c_uint32), ("query_route", C.c_uint32),
         ("ms_normals", C.c_double), ("n_normal_chunks", C.c_uint32),
         ("ms_outliers", C.c_double), ("n_outlier_chunks", C.c_uint32),
+        ("ms_voxel", C.c_double), ("n_voxel_passes", C.c_uint32),
     ]
 
 
@@ -61,6 +62,11 @@ class ExchangeStats(C.Structure):
 class OutlierResult(C.Structure):
     """pt_outlier_result_t"""
     _fields_ = [("n_before", C.c_uint64), ("n_kept", C.c_uint64), ("n_scored", C.c_uint64), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
+
+
+class VoxelResult(C.Structure):
+    """pt_voxel_result_t"""
+    _fields_ = [("n_before", C.c_uint64), ("n_voxels", C.c_uint64), ("max_count", C.c_uint32), ("dims", C.c_uint32 * 3), ("origin", C.c_double * 3), ("voxel", C.c_double)]
 
 
 class PtError(RuntimeError):
@@ -121,6 +127,7 @@ def lib():
         "pt_pca_normals_dev": (i32, [p, p, u64, i32, p]),
         "pt_estimate_normals": (i32, [p, i32, i32, C.POINTER(C.c_double), p, i32]),
         "pt_remove_outliers": (i32, [p, i32, i32, dbl, i32, p, p, i32, C.POINTER(OutlierResult)]),
+        "pt_voxel_downsample": (i32, [p, dbl, C.POINTER(C.c_double), i32, p, p, i32, C.POINTER(VoxelResult)]),
         "pt_merge_candidates_dev": (i32, [p, p, p, i32, u64, i32, p, p]),
         "pt_slab_need_dev": (i32, [p, p, i32, p, u64, i32, i32, p, i32, i32, p]),
         "pt_pack_requests_dev": (i32, [p, p, i32, p, u64, i32, i32, p, i32, i32, p, p, p]),

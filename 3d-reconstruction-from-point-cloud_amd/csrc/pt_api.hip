@@ -61,8 +61,9 @@ enum Slot : int {
   RB_DEDUP = 2,        // 2 words: leaves, records (rebuild, dedup_leaves)
   RB_TODO = 4,         // 1 word: targets the tile kernel left over (run_query)
   RB_RETRY = 5,        // 1 word: blocks for the tile kernel's second chance (run_query)
-  RB_COUNT = 6,        // 1 word: packets of pt_pack_requests_dev / targets in reach of a chunk (pt_stream_query) / points pt_remove_outliers keeps
-  RB_TLIST = 7,        // 1 word: blocks that hold targets (run_query, sparse tile launch)
+  RB_COUNT = 6,        // 1 word: packets of pt_pack_requests_dev / targets in reach of a chunk (pt_stream_query) / points pt_remove_outliers keeps /
+                       // occupied voxels (pt_voxel_downsample)
+  RB_TLIST = 7,        // 1 word: blocks that hold targets (run_query, sparse tile launch) / members of the fullest voxel (pt_voxel_downsample)
   RB_OCC = 8,          // 2 words: sum, max (rebuild, occupied cells and the fullest one)
   RB_NODES = 10,       // 1 word: nodes of the refinement so far (rebuild)
   RB_PROBE = 11,       // 1 word, host only: the uniform probe's flag, read back from device word RB_PROBE_DEV (rebuild)
@@ -131,6 +132,7 @@ struct pt_ctx {
   uint64_t normals_chunk = 8u << 20;      // "normals_chunk": points per chunk of the self-query passes (pt_estimate_normals, pt_remove_outliers)
   hipEvent_t nev[2] = {nullptr, nullptr}; // ... and their timing (run_query uses ev[0..2] itself)
   DevBuf outl;                   // pt_remove_outliers: scores (8 n), kept indices (4 n), mask (n), tile offsets, reduction partials, result words
+  DevBuf vox;                    // pt_voxel_downsample: two (key, index) buffers, voxel starts, voxel_of, the sort's histograms, tile offsets
   bool posattr_valid = false;
   Learned learned;
   bool slab() const { return ids != IdMode::whole; }
@@ -1149,7 +1151,7 @@ void pt_ctx_destroy(pt_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf* all[] = {&c->in_xyz, &c->in_gidx, &c->attr, &c->rec, &c->rec_tmp, &c->cell_start, &c->stb_mem, &c->t_xyz, &c->t_gidx, &c->trec,
                    &c->trec_tmp, &c->x_xyz, &c->ttb_mem, &c->bbox6, &c->counter, &c->q_idx, &c->q_d2, &c->b_rgb, &c->b_nrm, &c->aos_stage, &c->misc, &c->bounds, &c->todo, &c->posattr, &c->retry, &c->rec32, &c->up_rgb, &c->up_nrm, &c->x_bounds, &c->x_counts, &c->x_matrix, &c->x_off, &c->x_req, &c->x_row, &c->x_rreq,
-                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd, &c->pos16, &c->outl};
+                   &c->x_rxyz, &c->x_rbound, &c->x_ans_i, &c->x_ans_d, &c->x_back_i, &c->x_back_d, &c->x_flags, &c->x_rows, &c->cell_node, &c->nodes, &c->heavy, &c->near_node, &c->xyz32, &c->tlist, &c->x_ans_a, &c->x_back_a, &c->x_rattr, &c->l_idx, &c->cap_bnd, &c->pos16, &c->outl, &c->vox};
   for (DevBuf* b : all) release(c, *b);
   if (c->h_bbox) (void)hipHostFree(c->h_bbox);
   if (c->h_counter) (void)hipHostFree(c->h_counter);
@@ -1822,6 +1824,121 @@ int pt_remove_outliers(pt_ctx* c, int mode, int k, double param, int apply, uint
     HIPCHK(c, hipEventElapsedTime(&ms, c->nev[0], c->nev[1]));
     c->st.ms_outliers = ms;
     c->st.ms_sort_targets = ms_copy; c->st.ms_query = ms_search;      // (sums over the chunks, as pt_estimate_normals reports them)
+  }
+  return PT_OK;
+}
+
+// voxel-grid downsampling of the resident cloud (include/pt_api.h): exact bounding box -> dims and key width on the host -> keys -> stable
+// radix sort of (key, index) -> segment heads -> ordered voxel starts -> the segmented reduction -> (apply) the result points written in
+// the stored width through the sort's record buffers, and the grid built over them as over a new cloud
+int pt_voxel_downsample(pt_ctx* c, double voxel, const double* origin, int apply, uint32_t* voxel_of_out, uint32_t* count_out, int out_on_device,
+                        pt_voxel_result_t* result) {
+  if (!c) return PT_ERR_ARG;
+  if (result) *result = pt_voxel_result_t{};
+  if (!c->built) return fail(c, PT_ERR_STATE, "pt_voxel_downsample before a build");
+  if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "pt_voxel_downsample needs the whole cloud resident (not a slab)");
+  if (!(std::isfinite(voxel) && voxel > 0.0)) return fail(c, PT_ERR_ARG, "the voxel size must be finite and > 0, got %g", voxel);
+  if (origin)
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(origin[a])) return fail(c, PT_ERR_ARG, "the voxel origin is not finite");
+  c->st.ms_voxel = 0.0; c->st.n_voxel_passes = 0;
+  const uint64_t n = c->n;
+  if (!n) return PT_OK;
+  if (c->has_attr && c->n_total != n) return fail(c, PT_ERR_STATE, "the attribute table holds %llu records, the cloud %llu points", (unsigned long long)c->n_total, (unsigned long long)n);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventRecord(c->nev[0], c->stream));
+  // host wait 1: the exact box.  floor((p - o) / v) is monotone in p, so the box alone gives dims and the range check, with the kernel's expression
+  double mn[3], mx[3], o[3];
+  { int r = source_bbox(c, 1u, mn, mx); if (r != PT_OK) return r; }
+  uint32_t dims[3];
+  int bits[3], total_bits = 0;
+  for (int a = 0; a < 3; ++a) {
+    o[a] = origin ? origin[a] : mn[a];
+    const double lo = std::floor((mn[a] - o[a]) / voxel), hi = std::floor((mx[a] - o[a]) / voxel);
+    if (!(lo >= 0.0)) return fail(c, PT_ERR_ARG, "origin above the cloud (axis %d: origin %g, the cloud starts at %g)", a, o[a], mn[a]);
+    if (!(hi < 2097152.0)) return fail(c, PT_ERR_ARG, "voxel too small for the cloud's extent (axis %d needs %g voxels, at most 2^21)", a, hi + 1.0);
+    dims[a] = (uint32_t)hi + 1u;
+    bits[a] = 0;
+    while ((1u << bits[a]) < dims[a]) ++bits[a];
+    total_bits += bits[a];
+  }
+  const bool key64 = total_bits > 32;
+  const uint32_t n32 = (uint32_t)n, ntiles = pt_radix_tiles(n32), mtiles = pt_mark_tiles(n32), nslots = pt_voxel_slots(n32);
+  // one allocation: key a | key b | idx a | idx b | starts | voxel_of | histograms + scan scratch | tile offsets of the marks | two words.
+  // Once the sort is done the key buffer it did not end in holds the partials, the slot owners and the head marks, and the index buffer
+  // it did not end in the counts: nothing of those grows the allocation.
+  const size_t al = 256;
+  auto up = [&](size_t b) { return (b + al - 1) & ~(al - 1); };
+  const size_t aux_bytes = (size_t)nslots * (PT_VOXEL_PART_BYTES + 4) + n + 64;
+  const size_t key_bytes = up(std::max<size_t>(n * (key64 ? 8 : 4), aux_bytes)), idx_bytes = up(n * 4);
+  const size_t hist_bytes = up(((size_t)256 * ntiles + ntiles / 8 + 16) * 4), off_bytes = up(((size_t)mtiles + 4) * 3 * 4);
+  RES(c, c->vox, 2 * key_bytes + 4 * idx_bytes + hist_bytes + off_bytes + al);
+  uint8_t* base = (uint8_t*)c->vox.p;
+  void* key_a = base; void* key_b = base + key_bytes;
+  uint32_t* idx_a = (uint32_t*)(base + 2 * key_bytes);
+  uint32_t* idx_b = (uint32_t*)(base + 2 * key_bytes + idx_bytes);
+  uint32_t* start = (uint32_t*)(base + 2 * key_bytes + 2 * idx_bytes);
+  uint32_t* voxel_of = (uint32_t*)(base + 2 * key_bytes + 3 * idx_bytes);
+  uint32_t* hist = (uint32_t*)(base + 2 * key_bytes + 4 * idx_bytes);
+  uint32_t* hscan = hist + (size_t)256 * ntiles;
+  uint32_t* off1 = (uint32_t*)(base + 2 * key_bytes + 4 * idx_bytes + hist_bytes);
+  uint32_t* off2 = off1 + mtiles + 4;
+  uint32_t* scan = off2 + mtiles + 4;
+  uint32_t* maxc = (uint32_t*)(base + 2 * key_bytes + 4 * idx_bytes + hist_bytes + off_bytes);
+  by_coords(c->src_type, c->in_half, (const void*)c->in_xyz.p, [&](auto x, auto) { pt_launch_voxel_keys(x, n32, o, voxel, bits, key64, key_a, idx_a, c->stream); });
+  const int passes = pt_launch_radix_sort(key_a, key_b, idx_a, idx_b, n32, total_bits, key64, hist, hscan, c->stream);
+  c->st.n_voxel_passes = (uint32_t)passes;
+  const bool in_a = (passes & 1) == 0;
+  const void* skey = in_a ? key_a : key_b;
+  const uint32_t* sidx = in_a ? idx_a : idx_b;
+  uint8_t* aux = (uint8_t*)(in_a ? key_b : key_a);                  // partials | owners | marks
+  uint32_t* owner = (uint32_t*)(aux + (size_t)nslots * PT_VOXEL_PART_BYTES);
+  uint8_t* mark = (uint8_t*)(owner + nslots);
+  uint32_t* count = in_a ? idx_b : idx_a;
+  pt_launch_voxel_heads(skey, key64, n32, mark, c->stream);
+  pt_launch_mark_count(mark, n32, off1, off2, scan, c->stream);
+  pt_launch_mark_write(mark, n32, off1, off2, start, start, c->stream);
+  pt_launch_voxel_max_count(start, off1 + mtiles, n32, maxc, c->stream);
+  HIPCHK(c, hipGetLastError());
+  // host wait 2: the number of occupied voxels, which sizes the reduction (and the fullest voxel with it)
+  HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_COUNT, off1 + mtiles, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_counter + RB_TLIST, maxc, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint32_t nv = c->h_counter[RB_COUNT], max_count = c->h_counter[RB_TLIST];
+  if (!nv || nv > n32) return fail(c, PT_ERR_STATE, "internal: %u voxels from %u points", nv, n32);
+  if (result) {
+    result->n_before = n; result->n_voxels = nv; result->max_count = max_count; result->voxel = voxel;
+    for (int a = 0; a < 3; ++a) { result->dims[a] = dims[a]; result->origin[a] = o[a]; }
+  }
+  const size_t es = c->in_half ? sizeof(__half) : tsize(c->src_type);
+  VoxelReduce vr{};
+  vr.xyz = c->in_xyz.p; vr.n = n32; vr.attr = c->has_attr ? (const Attr*)c->attr.p : nullptr;
+  vr.idx = sidx; vr.start = start; vr.nv = nv; vr.voxel_of = voxel_of; vr.count = count;
+  vr.owner = owner; vr.part = aux; vr.nslots = nslots;
+  vr.apply = apply ? 1 : 0; vr.xyz_out = c->rec_tmp.p; vr.attr_out = (Attr*)c->rec.p;      // (the sort's record buffers: the rebuild overwrites both)
+  if (apply && (c->rec_tmp.cap < (size_t)nv * 3 * es || (c->has_attr && c->rec.cap < (size_t)nv * sizeof(Attr)))) return fail(c, PT_ERR_STATE, "internal: record buffers smaller than the cloud");
+  const bool blocked = max_count > PT_VOXEL_BLOCK;
+  if (c->in_half) pt_launch_voxel_reduce<__half>(vr, blocked, c->stream);
+  else if (c->src_type == PT_F64) pt_launch_voxel_reduce<double>(vr, blocked, c->stream);
+  else pt_launch_voxel_reduce<float>(vr, blocked, c->stream);
+  HIPCHK(c, hipGetLastError());
+  const hipMemcpyKind out_kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (voxel_of_out) HIPCHK(c, hipMemcpyAsync(voxel_of_out, voxel_of, n * sizeof(uint32_t), out_kind, c->stream));
+  if (count_out) HIPCHK(c, hipMemcpyAsync(count_out, count, (size_t)nv * sizeof(uint32_t), out_kind, c->stream));
+  if ((voxel_of_out || count_out) && !out_on_device) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (apply) {
+    HIPCHK(c, hipMemcpyAsync(c->in_xyz.p, c->rec_tmp.p, (size_t)nv * 3 * es, hipMemcpyDeviceToDevice, c->stream));
+    if (c->has_attr) HIPCHK(c, hipMemcpyAsync(c->attr.p, c->rec.p, (size_t)nv * sizeof(Attr), hipMemcpyDeviceToDevice, c->stream));
+    adopt_cloud(c, c->src_type, nv, nv, IdMode::whole, c->in_half, c->has_attr);     // a new whole cloud, as pt_remove_outliers ends
+    c->rec32_valid = false;
+    { int r = rebuild(c); if (r != PT_OK) return r; }
+  }
+  HIPCHK(c, hipEventRecord(c->nev[1], c->stream));
+  SETTLE(c, c->sync != 0);
+  if (c->sync) {
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->nev[0], c->nev[1]));
+    c->st.ms_voxel = ms;
   }
   return PT_OK;
 }

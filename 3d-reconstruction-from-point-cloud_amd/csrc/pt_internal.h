@@ -1,5 +1,5 @@
 // pt_internal.h -- host-side launch interface between the C-ABI glue (pt_api.hip) and the kernel
-// translation units (pt_grid.hip, pt_knn_group.hip / pt_knn_wave.hip / pt_knn_tile.hip, pt_query.hip, pt_attr.hip, pt_outlier.hip, ...).  Everything takes the stream to launch on;
+// translation units (pt_grid.hip, pt_knn_group.hip / pt_knn_wave.hip / pt_knn_tile.hip, pt_query.hip, pt_attr.hip, pt_outlier.hip, pt_voxel.hip, ...).  Everything takes the stream to launch on;
 // nothing here allocates or synchronises.
 #pragma once
 #include "pt_common.h"
@@ -214,6 +214,35 @@ void pt_launch_outlier_stats(const double* score, uint32_t n, double alpha, doub
 void pt_launch_outlier_mask(const double* score, uint32_t n, const double* res, int radius_mode, double full, uint8_t* keep, hipStream_t s);
 // out[p * nk + j] = in[p * in_stride + map[j]] for p < planes, elements of 2, 4, 8 or 16 bytes (map: the kept original indices, ascending)
 void pt_launch_gather(const void* in, size_t in_stride, size_t elem_bytes, const uint32_t* map, uint32_t nk, int planes, void* out, hipStream_t s);
+
+// ---- pt_voxel.hip: voxel-grid downsampling of the resident cloud (pt_voxel_downsample) ------------------------------
+constexpr uint32_t PT_VOXEL_BLOCK = 256;          // members per block of a voxel's blocked sum (include/pt_api.h: part of the definition)
+constexpr size_t PT_VOXEL_PART_BYTES = 64;        // one block's partial sums: six doubles (position, normal) and four colour sums
+// key[i] = (iz, iy, ix) of point i packed into bits[2] + bits[1] + bits[0] bits (z highest), i = floor((p - o) / v) per axis; idx[i] = i.
+// key: uint64_t[n] (key64) or uint32_t[n].  xyz: the planar cloud in the width it is held in (__half, float, double)
+template <class T>
+void pt_launch_voxel_keys(const T* xyz, uint32_t n, const double o[3], double v, const int bits[3], bool key64, void* key, uint32_t* idx, hipStream_t s);
+// Stable LSD radix sort of the (key, idx) pairs by the low `bits` bits of the key, 8 bits per pass, ping-pong between the a and the b
+// buffers: returns the number of passes run -- the result lies in the a buffers when it is even, in the b buffers when it is odd.
+// hist: 256 * pt_radix_tiles(n) words (per-tile digit counts, scanned in place); scan_tmp: pt_radix_tiles(n) / 8 + 2 words
+uint32_t pt_radix_tiles(uint32_t n);
+int pt_launch_radix_sort(void* key_a, void* key_b, uint32_t* idx_a, uint32_t* idx_b, uint32_t n, int bits, bool key64, uint32_t* hist, uint32_t* scan_tmp, hipStream_t s);
+// mark[i] = 1 where the sorted key changes (and at 0): pt_launch_mark_count / _write turn the marks into the voxels' ordered start positions
+void pt_launch_voxel_heads(const void* key, bool key64, uint32_t n, uint8_t* mark, hipStream_t s);
+// *max_out = members of the fullest voxel (start: the ordered starts, *nv_dev of them, both still on the device)
+void pt_launch_voxel_max_count(const uint32_t* start, const uint32_t* nv_dev, uint32_t n, uint32_t* max_out, hipStream_t s);
+// The segmented reduction.  voxel_of[idx] and count[j] are always written; with `apply` also result point j: planar xyz_out (stride nv, the
+// stored width) and attr_out[j] when attr is given.  blocked (some voxel holds more than PT_VOXEL_BLOCK members): those voxels are summed
+// in blocks through owner / part, pt_voxel_slots(n) entries of 4 / PT_VOXEL_PART_BYTES bytes each
+uint32_t pt_voxel_slots(uint32_t n);
+struct VoxelReduce {
+  const void* xyz; uint32_t n; const Attr* attr;
+  const uint32_t* idx; const uint32_t* start; uint32_t nv;
+  uint32_t* voxel_of; uint32_t* count;
+  uint32_t* owner; void* part; uint32_t nslots;
+  int apply; void* xyz_out; Attr* attr_out;
+};
+template <class T> void pt_launch_voxel_reduce(const VoxelReduce& r, bool blocked, hipStream_t s);
 
 // ---- pt_bake.hip ------------------------------------------------------------------------------
 // per-face texture bake (reference src/pointsTransfer.cpp:466-581, :66-107): every covered pixel of the R x R atlas does an

@@ -36,6 +36,11 @@
 //                    runs first; both run before --estimate-normals, and the search, transfer.ply, the texture and the normal map see the
 //                    filtered cloud.  stderr reports kept / removed / threshold / ms per filter.  Not with --synthetic, not with
 //                    --gpus N > 1 (a slab does not hold its points' neighbours; --gpus 1 runs unsharded): exit 2
+//   --voxel-downsample V  after the build and before the filters and --estimate-normals, thin the cloud to one point per occupied voxel of
+//                    side V (cloud units, V > 0; pt_voxel_downsample): the centroid of the voxel's points with their mean colour and mean
+//                    normal.  The grid starts at the cloud's per-axis minimum.  Everything after it -- the filters, the normals pass, the
+//                    search, transfer.ply, the texture and the normal map -- sees the thinned cloud.  stderr reports points before / after
+//                    and the fullest voxel.  Not with --synthetic, not with --gpus N > 1 (--gpus 1 runs unsharded): exit 2
 // There is no CPU path: without a usable GPU the tool reports the error and exits non-zero.
 #include <chrono>
 #include <cmath>
@@ -135,6 +140,8 @@ int main(int argc, char** argv) {
   int sor_k = 0, rad_min = 0;                      // --remove-outliers K ALPHA, --remove-isolated MIN R
   double sor_alpha = 0.0, rad_r = 0.0;
   bool sor_given = false, sor_ok = true, rad_given = false, rad_ok = true;
+  double vox = 0.0;                                // --voxel-downsample V
+  bool vox_given = false, vox_ok = true;
   std::string rendezvous;
   // --synthetic N M SEED [--clustered] [--xyz f32|f16|f64]: SURVEY.md Appendix C's generator instead of the two files (the positional
   // arguments are ignored): the BASELINE configurations run through this binary without a cloud on disk -- no mesh, so no texture
@@ -192,6 +199,13 @@ int main(int argc, char** argv) {
       if (sor) { sor_given = true; sor_k = (int)std::max(-1L, std::min(cnt, 1000L)); sor_alpha = x; sor_ok = parsed && cnt >= 2 && cnt <= PT_MAX_K && x >= 0.0; }
       else { rad_given = true; rad_min = (int)std::max(-1L, std::min(cnt, 1000L)); rad_r = x; rad_ok = parsed && cnt >= 1 && cnt <= PT_MAX_K - 1 && x > 0.0; }
     }
+    else if (a == "--voxel-downsample") {
+      const char* v = val();
+      char* end = nullptr;
+      vox = std::strtod(v, &end);
+      vox_given = true;
+      vox_ok = *v && end && !*end && std::isfinite(vox) && vox > 0.0;
+    }
     else { std::cerr << "unknown option " << a << std::endl; return 2; }
     for (int j = i_before; j <= i; ++j) passthrough.push_back(argv[j]);
   }
@@ -204,12 +218,15 @@ int main(int argc, char** argv) {
   if (vp_given && !vp_ok) { std::cerr << "--viewpoint needs three finite numbers" << std::endl; return 2; }
   if (est_given && synthetic) { std::cerr << "--estimate-normals / --viewpoint: not with --synthetic (the generated cloud has normals)" << std::endl; return 2; }
   if (est_given && (gpus > 1 || rank >= 0 || finalize)) { std::cerr << "--estimate-normals / --viewpoint: not with --gpus N > 1 (the pass needs the whole cloud on one GPU)" << std::endl; return 2; }
+  if (vox_given && !vox_ok) { std::cerr << "--voxel-downsample needs a finite voxel size V > 0" << std::endl; return 2; }
+  if (vox_given && synthetic) { std::cerr << "--voxel-downsample: not with --synthetic (generate fewer points instead)" << std::endl; return 2; }
+  if (vox_given && (gpus > 1 || rank >= 0 || finalize)) { std::cerr << "--voxel-downsample: not with --gpus N > 1 (the pass needs the whole cloud on one GPU)" << std::endl; return 2; }
   if (sor_given && !sor_ok) { std::cerr << "--remove-outliers needs K in [2, " << PT_MAX_K << "] and a finite ALPHA >= 0" << std::endl; return 2; }
   if (rad_given && !rad_ok) { std::cerr << "--remove-isolated needs MIN in [1, " << PT_MAX_K - 1 << "] and a finite R > 0" << std::endl; return 2; }
   const char* filter_flags = sor_given && rad_given ? "--remove-outliers / --remove-isolated" : (sor_given ? "--remove-outliers" : "--remove-isolated");
   if ((sor_given || rad_given) && synthetic) { std::cerr << filter_flags << ": not with --synthetic (the generated cloud has no strays)" << std::endl; return 2; }
   if ((sor_given || rad_given) && (gpus > 1 || rank >= 0 || finalize)) { std::cerr << filter_flags << ": not with --gpus N > 1 (a slab does not hold its points' neighbours)" << std::endl; return 2; }
-  if ((est_given || sor_given || rad_given) && gpus == 1) gpus = 0;            // (one GPU: the unsharded path, which holds the whole cloud)
+  if ((est_given || sor_given || rad_given || vox_given) && gpus == 1) gpus = 0;            // (one GPU: the unsharded path, which holds the whole cloud)
   const bool capped = max_dist < INFINITY;
   // vertices whose list came back empty under the cap (reported on stderr and in --json; the stdout lines stay the reference's)
   auto count_empty = [&](const std::vector<uint32_t>& ids, size_t rows) {
@@ -347,6 +364,15 @@ int main(int argc, char** argv) {
   if (rc == PT_OK) rc = pt_upload_end(ctx);
   free_pinned();
   if (rc != PT_OK) { std::cerr << "pointsTransfer: build failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+  if (vox_given) {                                 // thinning first: the filters and the normals pass then run on the thinned cloud
+    pt_voxel_result_t vr;
+    rc = pt_voxel_downsample(ctx, vox, nullptr, 1, nullptr, nullptr, 0, &vr);
+    if (rc != PT_OK) { std::cerr << "pointsTransfer: --voxel-downsample failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+    pt_stats_t sv;
+    if (pt_stats(ctx, &sv) == PT_OK)
+      std::cerr << "[pt_hip] --voxel-downsample " << vox << ": " << vr.n_before << " points -> " << vr.n_voxels << " (one per occupied voxel of a " << vr.dims[0] << "x" << vr.dims[1]
+                << "x" << vr.dims[2] << " grid), fullest voxel " << vr.max_count << " points, " << sv.ms_voxel << " ms (device time)" << std::endl;
+  }
   for (int f = 0; f < 2; ++f) {                    // the filters, radius first (inside the build's line, like the normals pass)
     if (!(f == 0 ? rad_given : sor_given)) continue;
     pt_outlier_result_t orr;

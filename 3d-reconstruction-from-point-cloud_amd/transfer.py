@@ -341,6 +341,40 @@ class PointsTransfer:
         self._chk(self._L.pt_remove_outliers(self._h, mode, kk, param, 1 if apply else 0, _ptr(keep_dev), _ptr(scores_dev), 1, C.byref(res)))
         return {f[0]: getattr(res, f[0]) for f in res._fields_}
 
+    @staticmethod
+    def _voxel_origin(origin):
+        if origin is None:
+            return None
+        o = np.asarray(origin, np.float64).reshape(-1)
+        if o.shape != (3,):
+            raise ValueError("voxel_downsample: origin must have three components")
+        return (C.c_double * 3)(*o)
+
+    @staticmethod
+    def _voxel_info(res):
+        return {"n_before": res.n_before, "n_voxels": res.n_voxels, "max_count": res.max_count, "dims": list(res.dims), "origin": list(res.origin), "voxel": res.voxel}
+
+    def voxel_downsample(self, voxel, origin=None, apply=True):
+        """Thin the resident cloud to one point per occupied voxel of side `voxel` (pt_voxel_downsample): the centroid of the voxel's
+        members with their mean colour and mean (not renormalised) normal.  The grid starts at `origin` (x, y, z), default the cloud's
+        per-axis minimum.  Returns (voxel_of uint32 (n,): the voxel of every original point, counts uint32 (n_voxels,), info dict);
+        voxels are numbered in ascending (iz, iy, ix).  With apply=True the resident cloud (and its attribute table) becomes the
+        n_voxels result points in that order."""
+        n = self.num_source
+        voxel_of = np.zeros(n, np.uint32)
+        counts = np.zeros(n, np.uint32)
+        res = capi.VoxelResult()
+        self._chk(self._L.pt_voxel_downsample(self._h, float(voxel), self._voxel_origin(origin), 1 if apply else 0, _ptr(voxel_of), _ptr(counts), 0, C.byref(res)))
+        return voxel_of, counts[:res.n_voxels].copy(), self._voxel_info(res)
+
+    def voxel_downsample_dev(self, voxel_of_dev, counts_dev, voxel, origin=None, apply=True):
+        """The same with the uint32 (n,) voxel numbers and the uint32 counts (capacity n, the first n_voxels written) in device buffers
+        (either may be None); returns info."""
+        self._adopt_torch_stream()
+        res = capi.VoxelResult()
+        self._chk(self._L.pt_voxel_downsample(self._h, float(voxel), self._voxel_origin(origin), 1 if apply else 0, _ptr(voxel_of_dev), _ptr(counts_dev), 1, C.byref(res)))
+        return self._voxel_info(res)
+
     # -- native slab exchange over RCCL (SURVEY.md 8e) ---------------------------------------------
     @staticmethod
     def comm_unique_id():

@@ -125,6 +125,9 @@ typedef struct pt_stats_t {
   double ms_outliers;       /* pt_remove_outliers: device time of the last call -- every chunk's search and scores, the reductions, the mask, and under
                              * `apply` the compaction and the rebuild (HIP events) */
   uint32_t n_outlier_chunks; /* ... and the number of chunks it walked the cloud in */
+  double ms_voxel;          /* pt_voxel_downsample: device time of the last call -- bounding box, keys, sort, reduction, and under `apply` the write-back and
+                             * the rebuild (HIP events) */
+  uint32_t n_voxel_passes;  /* ... and the radix passes its sort ran: ceil(key bits / 8), 0 when every axis has one voxel */
 } pt_stats_t;
 enum {
   PT_ROUTE_TILE = 1,        /* the LDS tile kernel */
@@ -212,7 +215,10 @@ int  pt_set_stream(pt_ctx*, void* hip_stream);
  *   - pt_remove_outliers waits on the host wherever its query route waits, as pt_estimate_normals does, and once more for the reduction's
  *     result and n_kept, which size the compaction (under `apply` the rebuild waits as every build does); device outputs (keep_out,
  *     score_out with out_on_device) are ordered on the context's stream;
- *   - ms_outliers is refreshed under "sync" 1 only.
+ *   - ms_outliers is refreshed under "sync" 1 only;
+ *   - pt_voxel_downsample waits on the host twice -- for the bounding box, and for the number of occupied voxels, which sizes the reduction
+ *     -- and under `apply` as every build does; device outputs (voxel_of_out, count_out with out_on_device) are ordered on the context's
+ *     stream; ms_voxel is refreshed under "sync" 1 only.
  *
  * "max_dist" r (cloud units; r >= 0, +inf = off, the default; NaN or r < 0: PT_ERR_ARG): neighbours farther than r are not returned.
  * R2 = r * r is computed once in double, and a source point is in reach iff d2 <= R2 (d2 the metric above; inclusive, like
@@ -408,6 +414,56 @@ typedef struct pt_outlier_result_t {
 int  pt_remove_outliers(pt_ctx*, int mode, int k, double param, int apply,
                         uint8_t* keep_out_or_null, double* score_out_or_null, int out_on_device,
                         pt_outlier_result_t* result_or_null);
+
+/* pt_voxel_downsample: thin the resident cloud to one point per occupied voxel -- the centroid of the voxel's members, with their mean colour
+ * and mean normal -- on the device: nothing is read back, thinned on the host and uploaded again.  It is the first step of the clean-up
+ * stage: pt_remove_outliers and pt_estimate_normals cost a search per point and are normally run on the thinned cloud.  Needs a built,
+ * whole cloud: PT_ERR_STATE before a build (or when an attribute table is resident whose n_total differs from n), PT_ERR_UNSUPPORTED on a
+ * slab context (pt_build_soa_indexed, a slab of pt_build_synth, "local_ids").  fp32, fp16 and fp64 clouds alike.  "max_dist" plays no part.
+ * Arguments: `voxel` (the voxel's side, cloud units) must be finite and > 0, `origin3_or_null` NULL or three finite doubles: PT_ERR_ARG otherwise.
+ * Voxel of a point: coordinates are widened exactly to double; o is the caller's origin, or the exact per-axis minimum of the cloud (NULL);
+ *   per axis i = floor((p - o) / voxel), the subtraction and the division each rounded once (a true division, no reciprocal).  The expression is
+ *   monotone in p, so dims[a] = floor((max_a - o_a) / voxel) + 1 -- the voxels from the origin to the cloud's far face -- and the range check
+ *   come from the bounding box alone.  Every index must lie in [0, 2^21): PT_ERR_ARG otherwise ("origin above the cloud": some point has a
+ *   negative index; "voxel too small for the cloud's extent"), with the cloud unchanged and nothing written.
+ * Order: occupied voxels are numbered 0 .. n_voxels - 1 in ascending (iz, iy, ix); a voxel's members are taken in ascending original index.
+ * Result point j, from the c members of voxel j ranked 0 .. c - 1:
+ *   position  per axis the BLOCKED SUM S of the coordinates as doubles, divided by (double)c with one division, rounded to the width the cloud
+ *             is held in: fp64 as is, fp32 by round-to-nearest-even, fp16 by rounding to fp32 FIRST and then to fp16, both nearest-even (a
+ *             direct double -> half conversion differs where the fp32 rounding lands on a tie of the fp16 grid);
+ *   blocked sum  P_b = the left-to-right sum, starting from its first term, of ranks [256 b, 256 (b + 1)); S = the left-to-right sum of P_0,
+ *             P_1, ...  For c <= 256 this is the plain sequential sum.  The order is a function of c alone -- of no tunable, route or device
+ *             -- and no floating-point atomic is used: results are bit-identical from run to run.  A one-member voxel reproduces its point;
+ *   colour    (attribute table resident) per byte of rgba the exact integer sum s of the members' bytes; the result byte is
+ *             (2 s + c) / (2 c) in integer arithmetic: the mean, rounded half up;
+ *   normal    per component the same blocked sum of the stored floats widened to double, divided by c, rounded to float.  NOT renormalised
+ *             -- pt_bake_maps' convention for mixed normals: a mean of unit normals is shorter than 1 where they disagree.  To get unit
+ *             normals back, run pt_estimate_normals on the thinned cloud.
+ * Outputs: voxel_of_out uint32[n_before], the voxel number of every original point; count_out uint32, capacity n_before, entries
+ *   [0, n_voxels) written; host or device memory according to out_on_device; either may be NULL.  result (may be NULL) is host memory.
+ *   n = 0: PT_OK, a zero result, nothing written.
+ * apply = 0: the resident cloud, the sorted records, the attribute table, the resident targets and what the context learned for its next
+ *   build are untouched, bit for bit (the scratch is the call's own, never the sort's record buffers).
+ * apply = 1: the resident cloud becomes the n_voxels result points in voxel order -- also when n_voxels == n_before: the order changes --
+ *   and the attribute table is replaced likewise when one is resident; everything derived from the old cloud is dropped and the grid is
+ *   built over the result as over a new cloud, exactly as pt_remove_outliers ends.  Afterwards EVERY entry point behaves as on a fresh
+ *   context on which pt_build_soa (+ attributes) was called with those arrays, bit for bit.  Resident targets are left as they were.
+ * Memory: with w = 4 or 8, the key's bytes (8 when the three axes need more than 32 bits together), the scratch is
+ *   (2 w + 16) n + n / 4 bytes: two (key, index) buffers (2 (w + 4) n), the voxel starts (4 n), voxel_of (4 n), and the sort's per-tile digit
+ *   counts (1 KB per 4096 points); 12 bytes per 2048 points of tile offsets on top.  The head marks, the counts, and for voxels of more
+ *   than 256 members the block partials (2 slots of 68 bytes per 256 points) live in the (key, index) buffer the sort did not end in.  The
+ *   scratch stays with the context until it is destroyed; under `apply` the result is written through the sort's record buffers, which the
+ *   rebuild overwrites anyway.
+ * pt_stats_t: ms_voxel, n_voxel_passes. */
+typedef struct pt_voxel_result_t {
+  uint64_t n_before, n_voxels;     /* points before; occupied voxels = points after */
+  uint32_t max_count;              /* members of the fullest voxel */
+  uint32_t dims[3];                /* voxels per axis, from the origin to the far face of the cloud's box */
+  double   origin[3], voxel;       /* as used */
+} pt_voxel_result_t;
+int  pt_voxel_downsample(pt_ctx*, double voxel, const double origin3_or_null[3], int apply,
+                         uint32_t* voxel_of_out_or_null, uint32_t* count_out_or_null, int out_on_device,
+                         pt_voxel_result_t* result_or_null);
 
 /* ---- multi-GPU merge ---------------------------------------------------------- */
 /* G-way merge of candidate lists under (d2, idx): lists are [g][m][k] device arrays. */
