@@ -14,7 +14,7 @@ MAX_K = 32
 F32, F16, F64 = 0, 1, 2
 DIST_UNIFORM, DIST_CLUSTERED = 0, 1
 BLEND_MEAN, BLEND_INV_D2 = 0, 1
-MAP_COLOR, MAP_NORMAL = 1, 2
+MAP_COLOR, MAP_NORMAL, MAP_HEIGHT = 1, 2, 4
 ORIENT_AXIS, ORIENT_VIEWPOINT = 0, 1
 OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -26,7 +26,7 @@ SYMBOLS = [
     "pt_num_source", "pt_query_aos", "pt_query_soa", "pt_targets_synth", "pt_targets_soa", "pt_targets_aos", "pt_num_targets", "pt_query_resident", "pt_query_blend_resident", "pt_query_resident_host",
     "pt_resident_target_ids", "pt_resident_target_xyz", "pt_resident_source_xyz", "pt_blend", "pt_blend_dev", "pt_blend_weighted", "pt_blend_weighted_dev", "pt_pca_normals",
     "pt_pca_normals_dev", "pt_estimate_normals", "pt_remove_outliers", "pt_voxel_downsample", "pt_merge_candidates_dev", "pt_slab_need_dev", "pt_pack_requests_dev", "pt_query_bounded_dev",
-    "pt_bake_texture", "pt_bake_maps", "pt_texture_pad", "pt_host_alloc", "pt_host_free", "pt_upload_begin", "pt_upload_range", "pt_upload_end", "pt_stream_query",
+    "pt_bake_texture", "pt_bake_maps", "pt_bake_maps_h", "pt_texture_pad", "pt_host_alloc", "pt_host_free", "pt_upload_begin", "pt_upload_range", "pt_upload_end", "pt_stream_query",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_comm_abort", "pt_exchange_merge_dev", "pt_exchange_merge_local", "pt_query_exchange_blend",
 ]
 
@@ -67,6 +67,11 @@ class OutlierResult(C.Structure):
 class VoxelResult(C.Structure):
     """pt_voxel_result_t"""
     _fields_ = [("n_before", C.c_uint64), ("n_voxels", C.c_uint64), ("max_count", C.c_uint32), ("dims", C.c_uint32 * 3), ("origin", C.c_double * 3), ("voxel", C.c_double)]
+
+
+class BakeResult(C.Structure):
+    """pt_bake_result_t"""
+    _fields_ = [("max_abs_height", C.c_double)]
 
 
 class PtError(RuntimeError):
@@ -134,6 +139,7 @@ def lib():
         "pt_query_bounded_dev": (i32, [p, p, i32, p, u64, i32, p, p]),
         "pt_bake_texture": (i32, [p, p, u64, p, u64, p, i32, i32, i32, p]),
         "pt_bake_maps": (i32, [p, p, u64, p, u64, p, i32, i32, i32, i32, p, p]),
+        "pt_bake_maps_h": (i32, [p, p, u64, p, u64, p, i32, i32, i32, i32, dbl, p, p, p, p]),
         "pt_texture_pad": (i32, [p, p, i32, i32, p]),
         "pt_host_alloc": (p, [u64]),
         "pt_host_free": (None, [p]),

@@ -2572,8 +2572,12 @@ int pt_exchange_merge_local(pt_ctx* const* ctxs, int g, const void* const* tgt_x
 }
 
 // ---- texture bake (pt_bake.hip) ------------------------------------------------------------------------------------
-int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
-                 int resolution, int pad_ksize, int maps, uint8_t* color_bgra_out, uint8_t* normal_bgra_out) {
+namespace {
+// pt_bake_maps (allowed = COLOR | NORMAL) and pt_bake_maps_h (allowed = all three) in one body: the checks in one order, one upload, one
+// face launch, then resolve / pad / copy out per requested plane
+int bake_planes(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
+                int resolution, int pad_ksize, int maps, int allowed, double height_range, uint8_t* color_bgra_out, uint8_t* normal_bgra_out,
+                uint8_t* height_bgra_out, pt_bake_result_t* result_or_null) {
   if (!c) return PT_ERR_ARG;
   if (c->src_type != PT_F32 && c->src_type != PT_F64) return fail(c, PT_ERR_STATE, "no source cloud resident (call a pt_build_* first)");
   if (c->slab()) return fail(c, PT_ERR_UNSUPPORTED, "the texture bake needs the whole cloud resident (not a slab)");
@@ -2581,24 +2585,35 @@ int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const in
   if (k < 1 || k > PT_MAX_K) return fail(c, PT_ERR_ARG, "k = %d out of range [1, %d]", k, PT_MAX_K);
   if (resolution < 1 || resolution > 32768) return fail(c, PT_ERR_ARG, "resolution out of range [1, 32768]");
   if (pad_ksize < 0 || (pad_ksize > 0 && !(pad_ksize & 1)) || pad_ksize > 255) return fail(c, PT_ERR_ARG, "pad_ksize must be 0 or an odd number <= 255");
-  if (maps < 1 || (maps & ~(PT_MAP_COLOR | PT_MAP_NORMAL))) return fail(c, PT_ERR_ARG, "maps = %d: a non-empty subset of PT_MAP_COLOR | PT_MAP_NORMAL", maps);
-  const bool want_c = (maps & PT_MAP_COLOR) != 0, want_n = (maps & PT_MAP_NORMAL) != 0;
-  if ((want_c && !color_bgra_out) || (want_n && !normal_bgra_out) || (nv && !mesh_vertices) || (nf && (!faces || !nbr_idx))) return fail(c, PT_ERR_ARG, "null argument");
+  if (maps < 1 || (maps & ~allowed))
+    return fail(c, PT_ERR_ARG, "maps = %d: a non-empty subset of PT_MAP_COLOR | PT_MAP_NORMAL%s", maps, (allowed & PT_MAP_HEIGHT) ? " | PT_MAP_HEIGHT" : "");
+  constexpr int NP = 3;                                    // planes in key order: colour, normal, height
+  uint8_t* const host[NP] = {color_bgra_out, normal_bgra_out, height_bgra_out};
+  const bool want[NP] = {(maps & PT_MAP_COLOR) != 0, (maps & PT_MAP_NORMAL) != 0, (maps & PT_MAP_HEIGHT) != 0};
+  const bool want_h = want[2];
+  if ((want[0] && !host[0]) || (want[1] && !host[1]) || (want[2] && !host[2]) || (nv && !mesh_vertices) || (nf && (!faces || !nbr_idx))) return fail(c, PT_ERR_ARG, "null argument");
+  if (want_h && !(height_range > 0.0 && std::isfinite(height_range))) return fail(c, PT_ERR_ARG, "height_range must be finite and > 0");
   if (nf >= (1ull << 24)) return fail(c, PT_ERR_ARG, "nf = %llu: the pixel key holds 24 bits of face index", (unsigned long long)nf);
   { int r = check_n(c, nv, "nv"); if (r) return r; }
+  if (result_or_null) result_or_null->max_abs_height = 0.0;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t npix = (size_t)resolution * (size_t)resolution;
-  // keys: one plane per requested map, the colour plane first; per map the resolved image and (padding) the padded one; tmp is shared
-  DevBuf keys, tex[2], out[2], tmp, dv, df, dn;
-  const size_t nplanes = (want_c ? 1 : 0) + (want_n ? 1 : 0);
-  uint8_t* const host[2] = {color_bgra_out, normal_bgra_out};
-  const bool want[2] = {want_c, want_n};
-  auto cleanup = [&]() { DevBuf* all[] = {&keys, &tex[0], &tex[1], &out[0], &out[1], &tmp, &dv, &df, &dn}; for (DevBuf* b : all) release(c, *b); };
+  // keys: one plane per requested map in key order (+ the height plane's two trailing words: max |h|, height_range); per map the
+  // resolved image and (padding) the padded one; tmp is shared
+  DevBuf keys, tex[NP], out[NP], tmp, dv, df, dn;
+  const size_t nplanes = (size_t)want[0] + (size_t)want[1] + (size_t)want[2];
+  const size_t key_bytes = nplanes * npix * 8 + (want_h ? BK_TRAILER * 8 : 0);
+  auto cleanup = [&]() {
+    DevBuf* all[] = {&keys, &tex[0], &tex[1], &tex[2], &out[0], &out[1], &out[2], &tmp, &dv, &df, &dn};
+    for (DevBuf* b : all) release(c, *b);
+  };
   auto run = [&]() -> int {
-    RES(c, keys, nplanes * npix * 8);
-    for (int p = 0; p < 2; ++p) if (want[p]) RES(c, tex[p], npix * 4);
+    RES(c, keys, key_bytes);
+    for (int p = 0; p < NP; ++p) if (want[p]) RES(c, tex[p], npix * 4);
     RES(c, dv, std::max<uint64_t>(nv, 1) * sizeof(pt_point)); RES(c, df, std::max<uint64_t>(nf, 1) * 12); RES(c, dn, std::max<uint64_t>(nv, 1) * (size_t)k * 4);
-    HIPCHK(c, hipMemsetAsync(keys.p, 0, nplanes * npix * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(keys.p, 0, key_bytes, c->stream));
+    unsigned long long* const trailer = (unsigned long long*)keys.p + nplanes * npix;
+    if (want_h) { int r = copy_in(c, trailer + 1, &height_range, 8, 0); if (r) return r; }
     { int r = copy_in(c, dv.p, mesh_vertices, nv * sizeof(pt_point), 0); if (r) return r; }
     { int r = copy_in(c, df.p, faces, nf * 12, 0); if (r) return r; }
     { int r = copy_in(c, dn.p, nbr_idx, nv * (size_t)k * 4, 0); if (r) return r; }
@@ -2613,10 +2628,11 @@ int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const in
       pt_launch_bake_faces<double>(x, x + c->n, x + 2 * c->n, (const Attr*)c->attr.p, (uint32_t)c->n, dv.p, (uint32_t)nv, (const int32_t*)df.p, (uint32_t)nf,
                                    (const uint32_t*)dn.p, k, resolution, maps, (unsigned long long*)keys.p, c->stream);
     }
-    const void* result[2] = {nullptr, nullptr};
-    for (int p = 0; p < 2; ++p) {
+    const void* result[NP] = {nullptr, nullptr, nullptr};
+    size_t plane = 0;
+    for (int p = 0; p < NP; ++p) {
       if (!want[p]) continue;
-      pt_launch_bake_resolve((const unsigned long long*)keys.p + (p && want_c ? npix : 0), (uint32_t*)tex[p].p, npix, c->stream);
+      pt_launch_bake_resolve((const unsigned long long*)keys.p + plane++ * npix, (uint32_t*)tex[p].p, npix, c->stream);
       result[p] = tex[p].p;
       if (pad_ksize > 0) {
         if (!tmp.p) RES(c, tmp, npix * 4);
@@ -2627,8 +2643,11 @@ int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const in
     }
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
-    for (int p = 0; p < 2; ++p) if (want[p]) HIPCHK(c, hipMemcpyAsync(host[p], result[p], npix * 4, hipMemcpyDeviceToHost, c->stream));
+    for (int p = 0; p < NP; ++p) if (want[p]) HIPCHK(c, hipMemcpyAsync(host[p], result[p], npix * 4, hipMemcpyDeviceToHost, c->stream));
+    double max_h = 0.0;                                    // (the slot holds the bit pattern of a non-negative double)
+    if (want_h && result_or_null) HIPCHK(c, hipMemcpyAsync(&max_h, trailer, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (result_or_null) result_or_null->max_abs_height = max_h;
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     c->st.ms_bake = ms;
@@ -2637,6 +2656,20 @@ int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const in
   const int r = run();
   cleanup();
   return r;
+}
+}  // namespace
+
+int pt_bake_maps(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
+                 int resolution, int pad_ksize, int maps, uint8_t* color_bgra_out, uint8_t* normal_bgra_out) {
+  return bake_planes(c, mesh_vertices, nv, faces, nf, nbr_idx, k, resolution, pad_ksize, maps, PT_MAP_COLOR | PT_MAP_NORMAL, 0.0, color_bgra_out, normal_bgra_out,
+                     nullptr, nullptr);
+}
+
+int pt_bake_maps_h(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,
+                   int resolution, int pad_ksize, int maps, double height_range, uint8_t* color_bgra_out, uint8_t* normal_bgra_out,
+                   uint8_t* height_bgra_out, pt_bake_result_t* result_or_null) {
+  return bake_planes(c, mesh_vertices, nv, faces, nf, nbr_idx, k, resolution, pad_ksize, maps, PT_MAP_COLOR | PT_MAP_NORMAL | PT_MAP_HEIGHT, height_range,
+                     color_bgra_out, normal_bgra_out, height_bgra_out, result_or_null);
 }
 
 int pt_bake_texture(pt_ctx* c, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf, const uint32_t* nbr_idx, int k,

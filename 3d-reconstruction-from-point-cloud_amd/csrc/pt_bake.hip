@@ -25,6 +25,13 @@
 //   * a mix of zero or non-finite length encodes (0, 0, 1);   * both planes carry the same key sequence, so the same (face, triangle)
 //     wins a pixel in both;   * the edge padding of the normal plane is the colour plane's (a per-channel maximum: the padded ring is
 //     NOT unit length).
+// Height map ("Height map"): a third key plane whose payload is the barycentric mix of the kept points' SIGNED
+// HEIGHTS over the face plane -- the third dot product of the projection, with the unit face normal e3 = n / |n|; a corner's is 0 --
+// divided by the caller's height_range H and encoded as a grey byte (0 -> 128, +H -> 255, -H -> 0, saturating).  A candidate's height
+// rides in a register from the projection to the slot fill (the same lane handles the same candidate in both), so the wave layout
+// grows by ph[] alone.  The call's two scalars travel behind the key planes (BK_TRAILER words): the maximum |h| over the interior kept
+// points, as the bit pattern of a non-negative double under atomicMax, and H -- the kernel's signature, and with it the colour-only
+// and colour / normal instantiations, stay as they were.
 // The map set is a compile-time property of the kernel (BakeCfg below): the colour-only kernel is the kernel this file always had,
 // instruction for instruction.
 //
@@ -54,8 +61,13 @@ struct BakeWave {
 struct BakeWaveN : BakeWave {              // the instantiations that write the normal plane
   double pnx[BK_MAXPTS], pny[BK_MAXPTS], pnz[BK_MAXPTS];   // the kept points' normals, as stored (not normalised)
 };
-constexpr int BK_COLOR = 1, BK_NORMAL = 2;   // = PT_MAP_COLOR, PT_MAP_NORMAL
-static_assert(sizeof(BakeWaveN) * BK_WAVES <= 64 * 1024, "the bake's LDS must fit the 64 KB static limit");
+struct BakeWaveH : BakeWave { double ph[BK_MAXPTS]; };     // the instantiations that write the height plane: the kept points' heights
+struct BakeWaveNH : BakeWaveN { double ph[BK_MAXPTS]; };
+constexpr int BK_COLOR = 1, BK_NORMAL = 2, BK_HEIGHT = 4;   // = PT_MAP_COLOR, PT_MAP_NORMAL, PT_MAP_HEIGHT
+constexpr int bk_planes(int maps) { return (maps & BK_COLOR ? 1 : 0) + (maps & BK_NORMAL ? 1 : 0) + (maps & BK_HEIGHT ? 1 : 0); }
+static_assert(sizeof(BakeWaveN) * BK_WAVES <= 64 * 1024 && sizeof(BakeWaveH) * BK_WAVES <= 64 * 1024 && sizeof(BakeWaveNH) * BK_WAVES <= 64 * 1024,
+              "the bake's LDS must fit the 64 KB static limit");
+static_assert(BK_TRAILER == 2, "behind the key planes: max |h| (bits of a non-negative double), then height_range");
 // The face kernel is a template on ONE type: the cloud's coordinate type for the colour-only kernel, WithMaps<coordinate type, map set>
 // for the instantiations that write the normal plane.  A plain second parameter (template <class T, int MAPS = BK_COLOR>) compiles the
 // same colour-only body, but renames the instantiation (bake_faces_kernel<float, 1>), and tools/isa_diff.py pairs kernels of two builds
@@ -64,7 +76,11 @@ static_assert(sizeof(BakeWaveN) * BK_WAVES <= 64 * 1024, "the bake's LDS must fi
 // behind a device function, even a forced-inline one, the compiler schedules the colour-only kernel differently.
 template <class T, int MAPS> struct WithMaps {};
 template <class C> struct BakeCfg { using Real = C; using Wave = BakeWave; static constexpr int maps = BK_COLOR; };
-template <class T, int M> struct BakeCfg<WithMaps<T, M>> { using Real = T; using Wave = BakeWaveN; static constexpr int maps = M; };
+template <class T, int M> struct BakeCfg<WithMaps<T, M>> {
+  using Real = T;
+  using Wave = std::conditional_t<(M & BK_HEIGHT) != 0, std::conditional_t<(M & BK_NORMAL) != 0, BakeWaveNH, BakeWaveH>, BakeWaveN>;
+  static constexpr int maps = M;
+};
 
 __device__ inline double cross2(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
 __device__ inline bool finite_d(double v) { return v == v && v - v == 0.0; }
@@ -93,11 +109,15 @@ __device__ inline bool in_circumcircle(const double* px, const double* py, int i
 struct TriNormals { double v[3][3]; unsigned long long* __restrict__ keys; };
 struct NoNormals {};
 template <int MAPS> using TriN = std::conditional_t<(MAPS & BK_NORMAL) != 0, TriNormals, NoNormals>;
+// ... and for the height plane: its vertices' heights, the range that maps to a byte, and the third key plane
+struct TriHeights { double h[3]; double range; unsigned long long* __restrict__ keys; };
+struct NoHeights {};
+template <int MAPS> using TriH = std::conditional_t<(MAPS & BK_HEIGHT) != 0, TriHeights, NoHeights>;
 
 // reference draw_triangle (:66-107), the wave's 64 lanes striding over the pixels of the bounding box that land inside the texture
 template <int MAPS>
 __device__ inline void draw_triangle(const double (&U)[3], const double (&V)[3], const uint32_t (&col)[3], int R, unsigned long long seq,
-                                     unsigned long long* __restrict__ keys, int lane, const TriN<MAPS> tn) {
+                                     unsigned long long* __restrict__ keys, int lane, const TriN<MAPS> tn, const TriH<MAPS> th = {}) {
   const double px = U[0] * R, py = V[0] * R, qx = U[1] * R, qy = V[1] * R, rx = U[2] * R, ry = V[2] * R;
   if (!(finite_d(px) && finite_d(py) && finite_d(qx) && finite_d(qy) && finite_d(rx) && finite_d(ry))) return;
   const double A = cross2(qx - px, qy - py, rx - px, ry - py);
@@ -143,11 +163,23 @@ __device__ inline void draw_triangle(const double (&U)[3], const double (&V)[3],
         }
         atomicMax(&tn.keys[(size_t)(R - j) * (size_t)R + (size_t)i], (seq << 32) | (unsigned long long)bgra);
       }
+      if constexpr ((MAPS & BK_HEIGHT) != 0) {             // the colour mix's shape on the heights, one grey byte
+        const double m = (b[0] * th.h[0] + b[1] * th.h[1]) + b[2] * th.h[2];
+        uint32_t g = 128u;                                 // a non-finite mix: zero height
+        if (finite_d(m)) {
+          const double t = m / th.range;
+          const double u = t * 127.5 + 127.5;
+          const double r = fmin(fmax(u + 0.5, 0.0), 255.0);
+          g = (uint32_t)(int)r;
+        }
+        atomicMax(&th.keys[(size_t)(R - j) * (size_t)R + (size_t)i], (seq << 32) | (unsigned long long)(0xFF000000u | g * 0x010101u));
+      }
     }
   }
 }
 
-// one face by one wave.  keys: one zeroed plane of R x R keys per map of the set, the colour plane first
+// one face by one wave.  keys: one zeroed plane of R x R keys per map of the set, in the order colour, normal, height; behind them,
+// when the set holds the height plane, BK_TRAILER words: max |h| (zeroed) and height_range
 template <class T>
 __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCfg<T>::Real* __restrict__ sx, const typename BakeCfg<T>::Real* __restrict__ sy,
                                                            const typename BakeCfg<T>::Real* __restrict__ sz,
@@ -167,6 +199,13 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCf
   constexpr bool NRM = (MAPS & BK_NORMAL) != 0;
   TriN<MAPS> tn;
   if constexpr (NRM) tn.keys = (MAPS & BK_COLOR) ? keys + (size_t)R * (size_t)R : keys;
+  constexpr bool HGT = (MAPS & BK_HEIGHT) != 0;
+  TriH<MAPS> th;
+  if constexpr (HGT) {
+    th.keys = keys + (size_t)(bk_planes(MAPS) - 1) * ((size_t)R * (size_t)R);
+    th.range = __longlong_as_double((long long)th.keys[(size_t)R * (size_t)R + 1]);
+    th.h[0] = 0.0; th.h[1] = 0.0; th.h[2] = 0.0;           // the corners lie in the plane
+  }
   uint32_t ccol[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -234,9 +273,16 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCf
       W.pny[lane] = lane == 0 ? tn.v[0][1] : (lane == 1 ? tn.v[1][1] : tn.v[2][1]);
       W.pnz[lane] = lane == 0 ? tn.v[0][2] : (lane == 1 ? tn.v[1][2] : tn.v[2][2]);
     }
+    if constexpr (HGT) W.ph[lane] = 0.0;
   }
   int np = 3;
   if (frame_ok && A != 0.0 && finite_d(A)) {
+    // unit face normal (height plane): e1, e2, e3 is right-handed; unusable -> every interior height is 0
+    [[maybe_unused]] double e3x = 0.0, e3y = 0.0, e3z = 0.0, hc[2] = {0.0, 0.0};
+    if constexpr (HGT) {
+      const double ln = sqrt((nx * nx + ny * ny) + nz * nz);
+      if (ln > 0.0 && finite_d(ln)) { e3x = nx / ln; e3y = ny / ln; e3z = nz / ln; }
+    }
     // ---- project the candidates, keep what is inside the face (:505-537) ----------------------------------------------
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -252,6 +298,7 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCf
         W.cx[e] = Xx; W.cy[e] = Xy;
         W.cu[e] = (b[0] * cu[0] + b[1] * cu[1]) + b[2] * cu[2];             // :571-572
         W.cv[e] = (b[0] * cv[0] + b[1] * cv[1]) + b[2] * cv[2];
+        if constexpr (HGT) hc[h] = (dx * e3x + dy * e3y) + dz * e3z;
       }
       if (e < BK_MAXNBR + 32) W.cin[e] = inside ? 1 : 0;
     }
@@ -279,15 +326,29 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCf
         W.px[slot] = W.cx[e]; W.py[slot] = W.cy[e]; W.pu[slot] = W.cu[e]; W.pv[slot] = W.cv[e];
         W.pc[slot] = attr[W.sorted[e]].rgba & 0xFFFFFFu;
         if constexpr (NRM) { const Attr a = attr[W.sorted[e]]; W.pnx[slot] = (double)a.nx; W.pny[slot] = (double)a.ny; W.pnz[slot] = (double)a.nz; }
+        if constexpr (HGT) W.ph[slot] = hc[h];
       }
     }
     np = 3 + (int)__popcll(m0) + (int)__popcll(m1);
+    if constexpr (HGT) {
+      // max |h| over the wave's interior kept points with a finite height; one atomic per wave, and none when it cannot raise the value
+      double mh = 0.0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) if (keep[h] && finite_d(hc[h])) mh = fmax(mh, fabs(hc[h]));
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) mh = fmax(mh, __shfl_xor(mh, d, 64));
+      if (lane == 0 && mh > 0.0) {
+        unsigned long long* const slot = th.keys + (size_t)R * (size_t)R;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(mh);      // monotone for non-negative doubles
+        if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < bits) atomicMax(slot, bits);
+      }
+    }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
   const unsigned long long seq0 = (unsigned long long)f * 256ull + 1ull;
   if (np == 3) {                                            // no interior points: the face itself (:540-544)
-    draw_triangle<MAPS>(cu, cv, ccol, R, seq0, keys, lane, tn);
+    draw_triangle<MAPS>(cu, cv, ccol, R, seq0, keys, lane, tn, th);
     return;
   }
   // ---- Delaunay by exhaustion: triples in lexicographic order, lanes over k (:546-581 with the build's definition) --------
@@ -326,7 +387,8 @@ __global__ __launch_bounds__(BK_WG) void bake_faces_kernel(const typename BakeCf
       tn.v[1][0] = W.pnx[b]; tn.v[1][1] = W.pny[b]; tn.v[1][2] = W.pnz[b];
       tn.v[2][0] = W.pnx[c]; tn.v[2][1] = W.pny[c]; tn.v[2][2] = W.pnz[c];
     }
-    draw_triangle<MAPS>(U, V, col, R, seq0 + (unsigned long long)t, keys, lane, tn);
+    if constexpr (HGT) { th.h[0] = W.ph[a]; th.h[1] = W.ph[b]; th.h[2] = W.ph[c]; }
+    draw_triangle<MAPS>(U, V, col, R, seq0 + (unsigned long long)t, keys, lane, tn, th);
   }
 }
 
@@ -378,9 +440,18 @@ void pt_launch_bake_faces(const T* sx, const T* sy, const T* sz, const Attr* att
   if (!nf) return;
   const dim3 grid((nf + BK_WAVES - 1) / BK_WAVES), wg(BK_WG);
   const unsigned char* verts = (const unsigned char*)verts_aos;
-  if (maps == BK_COLOR) hipLaunchKernelGGL(bake_faces_kernel<T>, grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys);
-  else if (maps == BK_NORMAL) hipLaunchKernelGGL((bake_faces_kernel<WithMaps<T, BK_NORMAL>>), grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys);
-  else hipLaunchKernelGGL((bake_faces_kernel<WithMaps<T, BK_COLOR | BK_NORMAL>>), grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys);
+#define BK_LAUNCH(...) hipLaunchKernelGGL((bake_faces_kernel<__VA_ARGS__>), grid, wg, 0, s, sx, sy, sz, attr, n, verts, nv, faces, nf, nbr, k, R, keys)
+  switch (maps) {
+    case BK_COLOR: BK_LAUNCH(T); break;
+    case BK_NORMAL: BK_LAUNCH(WithMaps<T, BK_NORMAL>); break;
+    case BK_COLOR | BK_NORMAL: BK_LAUNCH(WithMaps<T, BK_COLOR | BK_NORMAL>); break;
+    case BK_HEIGHT: BK_LAUNCH(WithMaps<T, BK_HEIGHT>); break;
+    case BK_HEIGHT | BK_COLOR: BK_LAUNCH(WithMaps<T, BK_HEIGHT | BK_COLOR>); break;
+    case BK_HEIGHT | BK_NORMAL: BK_LAUNCH(WithMaps<T, BK_HEIGHT | BK_NORMAL>); break;
+    case BK_HEIGHT | BK_NORMAL | BK_COLOR: BK_LAUNCH(WithMaps<T, BK_HEIGHT | BK_NORMAL | BK_COLOR>); break;
+    default: break;                                        // (the C ABI admits no other set)
+  }
+#undef BK_LAUNCH
 }
 template void pt_launch_bake_faces<float>(const float*, const float*, const float*, const Attr*, uint32_t, const void*, uint32_t, const int32_t*, uint32_t,
                                           const uint32_t*, int, int, int, unsigned long long*, hipStream_t);

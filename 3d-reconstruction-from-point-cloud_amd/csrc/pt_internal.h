@@ -252,6 +252,11 @@ template <class T> void pt_launch_voxel_reduce(const VoxelReduce& r, bool blocke
 // maps (PT_MAP_COLOR | PT_MAP_NORMAL, not 0): which key planes the one launch writes.  keys holds one zeroed plane of R x R keys per
 // map of the set, the colour plane first; the normal plane's payload is the per-pixel renormalised mix of the normals (corners: the
 // records' `normal`; interior points: attr's, as stored) under the same key sequence.  Each plane is resolved and padded on its own.
+// With PT_MAP_HEIGHT in the set (any subset of the three maps, plane order colour, normal, height) the height plane's payload is the
+// grey byte of the mixed signed heights over the face plane, and keys holds BK_TRAILER more words behind the planes: [0] zeroed by the
+// caller, on return the bit pattern of the non-negative double max |h| over the interior kept points; [1] the caller's height_range
+// (bit pattern of a double, finite and > 0).
+constexpr int BK_TRAILER = 2;
 template <class T>
 void pt_launch_bake_faces(const T* sx, const T* sy, const T* sz, const Attr* attr, uint32_t n, const void* verts_aos, uint32_t nv, const int32_t* faces,
                           uint32_t nf, const uint32_t* nbr, int k, int R, int maps, unsigned long long* keys, hipStream_t s);

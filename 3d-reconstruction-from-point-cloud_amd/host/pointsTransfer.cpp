@@ -16,6 +16,10 @@
 //   --out FILE       default transfer.ply ("" = do not write)      --device D           default 0
 //   --normal-map FILE  also bake the object-space normal map (pt_bake_maps: one face pass for both; with --texture "" the map alone);
 //                    not with --synthetic (no mesh: exit 2); under --gpus N the finalize process bakes it, as it bakes the texture
+//   --height-map FILE --height-range H  also bake the height map (pt_bake_maps_h, the same face pass): per texel the signed distance of the
+//                    cloud from the face along the face normal, grey, 128 = on the face, 255 = +H, 0 = -H (H finite, > 0, cloud units).
+//                    Each flag needs the other; not with --synthetic: exit 2.  stderr reports max |h| and warns when H is smaller (heights
+//                    beyond +-H saturate); --json adds height_range and max_abs_height; under --gpus N the finalize process bakes it
 //   --texture FILE   default texture.png ("" = no bake)            --resolution R       default 8192
 //   --pad K          edge-padding kernel, default 25 (0 = none)
 //   --neighbors FILE also dump the neighbour indices (binary u32[M][K])
@@ -129,6 +133,9 @@ int main(int argc, char** argv) {
   int K = 20, device = 0, mode = PT_BLEND_MEAN, ply_threads = 0, resolution = 8192, pad = 25;     // K, RESOLUTION: reference :128-129; 25: :594
   std::string out_name = "transfer.ply", nbr_name, tex_name = "texture.png";                      // texture.png: reference :615
   std::string nmap_name;                           // --normal-map FILE: the object-space normal map, baked beside the texture in one pt_bake_maps call ("" = none)
+  std::string hmap_name;                           // --height-map FILE: the height map, baked in the same call ("" = none); needs --height-range H
+  double height_range = 0.0;
+  bool hrange_given = false, hrange_ok = true;
   std::string json_name;                           // --json FILE: the phase times of the stdout lines + pt_stats as one JSON object
   int gpus = 0, rank = -1;
   double max_dist = INFINITY;                      // --max-dist R (+inf: off)
@@ -159,6 +166,14 @@ int main(int argc, char** argv) {
     else if (a == "--neighbors") nbr_name = val();
     else if (a == "--texture") tex_name = val();
     else if (a == "--normal-map") nmap_name = val();
+    else if (a == "--height-map") hmap_name = val();
+    else if (a == "--height-range") {
+      const char* v = val();
+      char* end = nullptr;
+      height_range = std::strtod(v, &end);
+      hrange_given = true;
+      hrange_ok = *v && end && !*end && std::isfinite(height_range) && height_range > 0.0;
+    }
     else if (a == "--json") json_name = val();
     else if (a == "--resolution") resolution = std::atoi(val());
     else if (a == "--pad") pad = std::atoi(val());
@@ -213,6 +228,10 @@ int main(int argc, char** argv) {
   if (resolution < 1 || resolution > 32768 || pad < 0 || pad > 255 || (pad > 0 && !(pad & 1))) { std::cerr << "--resolution must be in [1, 32768], --pad 0 or odd" << std::endl; return 2; }
   if (!max_dist_ok) { std::cerr << "--max-dist must be a number >= 0" << std::endl; return 2; }
   if (!nmap_name.empty() && synthetic) { std::cerr << "--normal-map needs a mesh: not with --synthetic" << std::endl; return 2; }
+  if (!hmap_name.empty() && !hrange_given) { std::cerr << "--height-map needs --height-range H" << std::endl; return 2; }
+  if (hrange_given && hmap_name.empty()) { std::cerr << "--height-range needs --height-map FILE" << std::endl; return 2; }
+  if (hrange_given && !hrange_ok) { std::cerr << "--height-range needs a finite H > 0" << std::endl; return 2; }
+  if (!hmap_name.empty() && synthetic) { std::cerr << "--height-map needs a mesh: not with --synthetic" << std::endl; return 2; }
   if (est_given && (est_k < 3 || est_k > PT_MAX_K)) { std::cerr << "--estimate-normals must be in [3, " << PT_MAX_K << "]" << std::endl; return 2; }
   if (vp_given && !est_given) { std::cerr << "--viewpoint needs --estimate-normals" << std::endl; return 2; }
   if (vp_given && !vp_ok) { std::cerr << "--viewpoint needs three finite numbers" << std::endl; return 2; }
@@ -239,6 +258,7 @@ int main(int argc, char** argv) {
     if (gpus < 1 || gpus > 64) { std::cerr << "--gpus must be in [1, 64]" << std::endl; return 2; }
     sharded::Options so;
     so.cloud = pc_file_name; so.mesh = mesh_file_name; so.out_name = out_name; so.tex_name = tex_name; so.nmap_name = nmap_name; so.rendezvous = rendezvous;
+    so.hmap_name = hmap_name; so.height_range = height_range;
     so.K = K; so.device = device; so.mode = mode; so.ply_threads = ply_threads; so.resolution = resolution; so.pad = pad; so.gpus = gpus; so.rank = rank;
     so.max_dist = max_dist;
     if (rank >= 0) return rank < gpus && !rendezvous.empty() ? sharded::run_rank(so) : 2;
@@ -426,13 +446,16 @@ int main(int argc, char** argv) {
   const double t_blend = since(t_task);
   t_task = clk::now();
   // the reference's face loop after the search (:484-581) and its post-processing (:593-611), on the GPU
-  std::vector<uint8_t> texture, normal_map;
-  if (!tex_name.empty() || !nmap_name.empty()) {
-    const int maps = (tex_name.empty() ? 0 : PT_MAP_COLOR) | (nmap_name.empty() ? 0 : PT_MAP_NORMAL);      // both in one face pass
+  std::vector<uint8_t> texture, normal_map, height_map;
+  pt_bake_result_t baked = {0.0};
+  if (!tex_name.empty() || !nmap_name.empty() || !hmap_name.empty()) {
+    const int maps = (tex_name.empty() ? 0 : PT_MAP_COLOR) | (nmap_name.empty() ? 0 : PT_MAP_NORMAL) | (hmap_name.empty() ? 0 : PT_MAP_HEIGHT);      // all in one face pass
     if (maps & PT_MAP_COLOR) texture.resize((size_t)resolution * (size_t)resolution * 4);
     if (maps & PT_MAP_NORMAL) normal_map.resize((size_t)resolution * (size_t)resolution * 4);
-    rc = pt_bake_maps(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, idx.data(), K, resolution,
-                      pad, maps, texture.empty() ? nullptr : texture.data(), normal_map.empty() ? nullptr : normal_map.data());
+    if (maps & PT_MAP_HEIGHT) height_map.resize((size_t)resolution * (size_t)resolution * 4);
+    rc = pt_bake_maps_h(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, idx.data(), K, resolution,
+                        pad, maps, height_range, texture.empty() ? nullptr : texture.data(), normal_map.empty() ? nullptr : normal_map.data(),
+                        height_map.empty() ? nullptr : height_map.data(), &baked);
     if (rc != PT_OK) { std::cerr << "pointsTransfer: texture bake failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
   }
   const double t_bake = since(t_task);
@@ -446,6 +469,11 @@ int main(int argc, char** argv) {
   }
   if (!nmap_name.empty() && !png::write_bgra(nmap_name, normal_map.data(), resolution, resolution)) {
     std::cerr << "pointsTransfer: cannot write " << nmap_name << std::endl;
+    pt_ctx_destroy(ctx);
+    return 1;
+  }
+  if (!hmap_name.empty() && !png::write_bgra(hmap_name, height_map.data(), resolution, resolution)) {
+    std::cerr << "pointsTransfer: cannot write " << hmap_name << std::endl;
     pt_ctx_destroy(ctx);
     return 1;
   }
@@ -481,10 +509,12 @@ int main(int argc, char** argv) {
       for (const char ch : nmap_name) { if (ch == '"' || ch == '\\') j << '\\'; j << ch; }
       j << "\"";
     }
+    if (!hmap_name.empty()) { j.precision(17); j << ", \"height_range\": " << height_range << ", \"max_abs_height\": " << baked.max_abs_height; }
     j << "}\n";
     if (!j) std::cerr << "pointsTransfer: cannot write " << json_name << std::endl;
   }
   if (capped) std::cerr << "[pt_hip] " << n_empty << " of " << M << " vertices have no point within " << max_dist << std::endl;
+  if (!hmap_name.empty()) sharded::report_heights(baked.max_abs_height, height_range);
   if (pt_stats(ctx, &st) == PT_OK)
     std::cerr << "[pt_hip] grid " << st.grid_dim[0] << "x" << st.grid_dim[1] << "x" << st.grid_dim[2] << " cells, build " << st.ms_build
               << " ms, target sort " << st.ms_sort_targets << " ms, kNN " << st.ms_query << " ms, blend " << st.ms_blend << " ms, texture bake " << st.ms_bake << " ms (device time)"

@@ -54,10 +54,20 @@ struct Options {
   std::string cloud, mesh, out_name = "transfer.ply", tex_name = "texture.png", nmap_name, rendezvous;      // nmap_name: --normal-map ("" = none)
   int K = 20, device = 0, mode = PT_BLEND_MEAN, ply_threads = 0, resolution = 8192, pad = 25, gpus = 1, rank = -1;
   double max_dist = INFINITY;       // --max-dist (every rank sets the same cap: pt_api.h "max_dist")
+  std::string hmap_name;            // --height-map ("" = none) and its --height-range
+  double height_range = 0.0;
   bool finalize = false;
 };
 using clk = std::chrono::steady_clock;
 inline double since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
+
+// what stderr says about a baked height map (both the single-process and the finalize path)
+inline void report_heights(double max_abs_height, double height_range) {
+  const auto prec = std::cerr.precision(9);
+  std::cerr << "[pt_hip] height map: max |h| " << max_abs_height << ", range +-" << height_range << std::endl;
+  if (height_range < max_abs_height) std::cerr << "[pt_hip] warning: --height-range " << height_range << " < max |h|: heights beyond +-H saturate" << std::endl;
+  std::cerr.precision(prec);
+}
 
 struct RefPoint { uint32_t id; double x, y, z; uint8_t rgb[3]; float nrm[3]; };      // (nrm: what the normal map mixes)
 
@@ -363,20 +373,24 @@ inline int run_finalize(const Options& o, WritePly&& write_ply) {
     const auto it = std::lower_bound(pts.begin(), pts.end(), idx[e], [](const RefPoint& a, uint32_t id) { return a.id < id; });
     local[e] = (it != pts.end() && it->id == idx[e]) ? (uint32_t)(it - pts.begin()) : PT_NOIDX;
   }
-  std::vector<uint8_t> texture, normal_map;
-  if (!o.tex_name.empty() || !o.nmap_name.empty()) {
+  std::vector<uint8_t> texture, normal_map, height_map;
+  if (!o.tex_name.empty() || !o.nmap_name.empty() || !o.hmap_name.empty()) {
     pt_ctx* ctx = nullptr;
     int dev = o.device;
     int rc = pt_ctx_create(&ctx, &dev, 1);
     if (rc != PT_OK) { std::cerr << "pointsTransfer: no usable HIP device for the texture bake" << std::endl; return 1; }
     rc = pt_build_soa(ctx, cxyz.data(), PT_F64, crgb.data(), cnrm.data(), np, 0);
-    const int maps = (o.tex_name.empty() ? 0 : PT_MAP_COLOR) | (o.nmap_name.empty() ? 0 : PT_MAP_NORMAL);      // both in one face pass
+    const int maps = (o.tex_name.empty() ? 0 : PT_MAP_COLOR) | (o.nmap_name.empty() ? 0 : PT_MAP_NORMAL) | (o.hmap_name.empty() ? 0 : PT_MAP_HEIGHT);      // all in one face pass
     if (maps & PT_MAP_COLOR) texture.resize((size_t)o.resolution * (size_t)o.resolution * 4);
     if (maps & PT_MAP_NORMAL) normal_map.resize((size_t)o.resolution * (size_t)o.resolution * 4);
+    if (maps & PT_MAP_HEIGHT) height_map.resize((size_t)o.resolution * (size_t)o.resolution * 4);
+    pt_bake_result_t baked = {0.0};
     if (rc == PT_OK)
-      rc = pt_bake_maps(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, local.data(), o.K, o.resolution,
-                        o.pad, maps, texture.empty() ? nullptr : texture.data(), normal_map.empty() ? nullptr : normal_map.data());
+      rc = pt_bake_maps_h(ctx, reinterpret_cast<const pt_point*>(mesh.vertices.data()), M, mesh.faces.data(), mesh.faces.size() / 3, local.data(), o.K, o.resolution,
+                          o.pad, maps, o.height_range, texture.empty() ? nullptr : texture.data(), normal_map.empty() ? nullptr : normal_map.data(),
+                          height_map.empty() ? nullptr : height_map.data(), &baked);
     if (rc != PT_OK) { std::cerr << "pointsTransfer: texture bake failed: " << pt_last_error(ctx) << std::endl; pt_ctx_destroy(ctx); return 1; }
+    if (!o.hmap_name.empty()) report_heights(baked.max_abs_height, o.height_range);
     pt_ctx_destroy(ctx);
   }
   if (o.max_dist < INFINITY) {
@@ -388,6 +402,7 @@ inline int run_finalize(const Options& o, WritePly&& write_ply) {
   t_task = clk::now();
   if (!o.tex_name.empty() && !png::write_bgra(o.tex_name, texture.data(), o.resolution, o.resolution)) { std::cerr << "pointsTransfer: cannot write " << o.tex_name << std::endl; return 1; }
   if (!o.nmap_name.empty() && !png::write_bgra(o.nmap_name, normal_map.data(), o.resolution, o.resolution)) { std::cerr << "pointsTransfer: cannot write " << o.nmap_name << std::endl; return 1; }
+  if (!o.hmap_name.empty() && !png::write_bgra(o.hmap_name, height_map.data(), o.resolution, o.resolution)) { std::cerr << "pointsTransfer: cannot write " << o.hmap_name << std::endl; return 1; }
   if (!o.out_name.empty()) write_ply(mesh, rgb, nrm);
   std::cout << "Output time: " << since(t_task) << " seconds" << std::endl;
   return 0;

@@ -462,6 +462,27 @@ class PointsTransfer:
         self._chk(self._L.pt_bake_maps(self._h, _ptr(v), v.shape[0], _ptr(f), f.shape[0], _ptr(nb), nb.shape[1], resolution, pad_ksize, maps, _ptr(col), _ptr(nrm)))
         return col, nrm
 
+    def bake_maps_h(self, mesh_vertices, faces, nbr_idx, resolution=8192, pad_ksize=0, color=True, normals=True, height_range=None):
+        """bake_maps with a third plane in the same launch: the height map, per texel the signed distance of the cloud from the face along
+        the face normal (a corner's is 0), divided by height_range and encoded grey: 0 -> 128, +height_range -> 255, -height_range -> 0,
+        saturating.  height_range=None: no height plane.  Returns (bgra, normal_bgra, height_bgra, info), None for planes not asked
+        for; info["max_abs_height"] is the largest |height| of an interior point (0.0 without the height plane): bake once to learn
+        it, then choose height_range."""
+        height = height_range is not None
+        if not (color or normals or height):
+            raise ValueError("bake_maps_h: ask for at least one of color, normals, height_range")
+        v = np.ascontiguousarray(mesh_vertices)
+        assert v.dtype.itemsize == 80
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        nb = np.ascontiguousarray(nbr_idx, dtype=np.uint32)
+        assert nb.ndim == 2 and nb.shape[0] == v.shape[0]
+        col, nrm, hgt = (np.empty((resolution, resolution, 4), np.uint8) if w else None for w in (color, normals, height))
+        maps = (capi.MAP_COLOR if color else 0) | (capi.MAP_NORMAL if normals else 0) | (capi.MAP_HEIGHT if height else 0)
+        res = capi.BakeResult()
+        self._chk(self._L.pt_bake_maps_h(self._h, _ptr(v), v.shape[0], _ptr(f), f.shape[0], _ptr(nb), nb.shape[1], resolution, pad_ksize, maps,
+                                         float(height_range) if height else 0.0, _ptr(col), _ptr(nrm), _ptr(hgt), C.byref(res)))
+        return col, nrm, hgt, {"max_abs_height": res.max_abs_height}
+
     def texture_pad(self, bgra, ksize=25):
         a = np.ascontiguousarray(bgra, dtype=np.uint8)
         assert a.ndim == 3 and a.shape[0] == a.shape[1] and a.shape[2] == 4

@@ -87,7 +87,7 @@ typedef struct pt_stats_t {
   int32_t n_refine;         /* how many times the last build refined its cell size */
   int32_t bbox_guess;       /* last build: 0 the bounding box came from a pass of its own; 1 the grid was laid out from a sampled
                              * box and pass 1 verified it (big clouds); -1 the sampled box was too small and the build was redone */
-  double ms_bake;           /* texture bake (+ edge padding) of the last pt_bake_texture / pt_bake_maps, device time */
+  double ms_bake;           /* texture bake (+ edge padding) of the last pt_bake_texture / pt_bake_maps / pt_bake_maps_h, device time */
   uint32_t n_nodes;         /* last build: refined ("heavy") cells and sub-cells that carry an 8x8x8 sub-grid (0: none needed) */
   int32_t refine_levels;    /* ... and how many levels deep (<= 3) */
   uint32_t max_cell_points; /* points of the fullest grid cell of the last build (adaptive builds) */
@@ -595,6 +595,38 @@ enum { PT_MAP_COLOR = 1, PT_MAP_NORMAL = 2 };
 int  pt_bake_maps(pt_ctx*, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf,
                   const uint32_t* nbr_idx, int k, int resolution, int pad_ksize, int maps,
                   uint8_t* color_bgra_out, uint8_t* normal_bgra_out);
+/* pt_bake_maps_h: pt_bake_maps with a third plane, the HEIGHT MAP -- per texel the signed distance of the cloud from the face along
+ * the face normal, the offset that parallax and displacement shaders read -- in the same call: one upload, one face launch whatever
+ * `maps` is.  `maps` is a non-empty subset of PT_MAP_COLOR | PT_MAP_NORMAL | PT_MAP_HEIGHT; an output whose bit is set must be non-null,
+ * one whose bit is clear is ignored (may be NULL).  height_range (H) must be finite and > 0 when PT_MAP_HEIGHT is set (PT_ERR_ARG
+ * otherwise) and is ignored when it is clear.  State rules, the other errors and pt_stats_t.ms_bake are pt_bake_maps's (a resident
+ * attribute table, PT_ERR_UNSUPPORTED on slab contexts, nf < 2^24), and pt_bake_maps IS the maps-within-{COLOR, NORMAL} case of this
+ * call (same bytes); pt_bake_maps itself still refuses PT_MAP_HEIGHT.
+ * The height map ("Height map"), all in double, every operation rounded on its own:
+ *   face normal     with a = c1 - c0, b = c2 - c0, n = a x b:  ln = sqrt((nx nx + ny ny) + nz nz),  e3 = n / ln.  e1, e2, e3 (the bake's
+ *                   plane frame) is right-handed: positive height is the side the face's winding faces
+ *   heights         a corner's is 0; an interior kept point's is h = (dx e3x + dy e3y) + dz e3z with d = the source point (widened
+ *                   exactly to double) - c0, the differences the projection forms.  Unless 0 < ln < inf every interior point of the
+ *                   face has h = 0
+ *   per pixel       m = (b0 h0 + b1 h1) + b2 h2 with the barycentrics b of the colour mix.  m not finite: byte = 128.  Otherwise
+ *                   t = m / H,  u = t * 127.5 + 127.5,  byte = (int)min(max(u + 0.5, 0), 255):  0 -> 128, +H -> 255, -H -> 0, saturating
+ *   pixel           {byte, byte, byte, 255} in B, G, R, A order (grey, so the padding's per-channel maximum and the PNG writer agree)
+ * The same (face, triangle) wins a pixel in every requested plane, so their alpha channels are equal; untouched pixels are 0.  A face
+ * with no interior point is 128 throughout.  Along a face's own edges the interior points' barycentrics vanish, so the height there
+ * is 0: the field is continuous across faces and pinned to the mesh at its edges.  pad_ksize > 0 pads the height plane exactly like
+ * the colour plane.
+ * result_or_null->max_abs_height: the maximum of |h| over all interior kept points whose h is finite, across all well-formed faces;
+ * 0 when there is none or when PT_MAP_HEIGHT is clear.  A maximum does not depend on the order of its terms: it is exact and the same
+ * on every run.  The weights are >= 0 and sum to 1, so H >= max_abs_height means nothing saturates (up to the last rounding): bake
+ * once with any H to learn it, then choose H.
+ * Device memory while the call runs, with P = resolution^2 pixels and m <= 3 maps: 8 m P (keys) + 4 m P (resolved planes), and with
+ * padding 4 m P + 4 P more -- all held until the planes are copied out: 3.4 GB for three padded maps at 8192^2. */
+enum { PT_MAP_HEIGHT = 4 };
+typedef struct pt_bake_result_t { double max_abs_height; } pt_bake_result_t;
+int  pt_bake_maps_h(pt_ctx*, const pt_point* mesh_vertices, uint64_t nv, const int32_t* faces, uint64_t nf,
+                    const uint32_t* nbr_idx, int k, int resolution, int pad_ksize, int maps, double height_range,
+                    uint8_t* color_bgra_out, uint8_t* normal_bgra_out, uint8_t* height_bgra_out,
+                    pt_bake_result_t* result_or_null);
 /* The edge padding alone (reference :593-611) on a host BGRA image. */
 int  pt_texture_pad(pt_ctx*, const uint8_t* bgra_in, int resolution, int ksize, uint8_t* bgra_out);
 

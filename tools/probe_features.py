@@ -1,5 +1,5 @@
 """Timings of the round-2 entry points on one GPU (dev probe; the numbers quoted in DESIGN.md sections 7-9):
-  bake     : pt_bake_texture, then pt_bake_maps with both maps, on a grid mesh over a uniform cloud (PT_PROBE_BAKE_REPS timed calls each, default 5)
+  bake     : pt_bake_texture, pt_bake_maps (both maps, normals only), then pt_bake_maps_h (colour + height, all three planes, height only), on a grid mesh over a uniform cloud (PT_PROBE_BAKE_REPS timed calls each, default 5)
   stream   : pt_stream_query, host-resident cloud in chunks, against the resident search of the same cloud
   exchange : pt_exchange_merge_local, G logical slabs of a uniform cloud (phase times from the library's stats)
 usage: python tools/probe_features.py [bake] [stream] [exchange]"""
@@ -40,7 +40,10 @@ if "bake" in what:
         reps = int(os.environ.get("PT_PROBE_BAKE_REPS", "5"))
         calls = (("pt_bake_texture", lambda: p.bake_texture(verts, faces, idx, resolution=R, pad_ksize=25)),
                  ("pt_bake_maps (colour + normals)", lambda: p.bake_maps(verts, faces, idx, resolution=R, pad_ksize=25)[0]),
-                 ("pt_bake_maps (normals only)", lambda: p.bake_maps(verts, faces, idx, resolution=R, pad_ksize=25, color=False)[1]))
+                 ("pt_bake_maps (normals only)", lambda: p.bake_maps(verts, faces, idx, resolution=R, pad_ksize=25, color=False)[1]),
+                 ("pt_bake_maps_h (colour + height)", lambda: p.bake_maps_h(verts, faces, idx, resolution=R, pad_ksize=25, normals=False, height_range=4e-4)[2]),
+                 ("pt_bake_maps_h (colour + normals + height)", lambda: p.bake_maps_h(verts, faces, idx, resolution=R, pad_ksize=25, height_range=4e-4)[2]),
+                 ("pt_bake_maps_h (height only)", lambda: p.bake_maps_h(verts, faces, idx, resolution=R, pad_ksize=25, color=False, normals=False, height_range=4e-4)[2]))
         for name, call in calls:
             dev = []
             for rep in range(reps + 1):                                              # the first call of each kind is the warm-up
